@@ -38,9 +38,12 @@ from .registry import MODELS
 # wins every stride-1 layer (1x1: conv_pw_kernel, 20-35 % ahead; 3x3 up to 256 channels: 10-25 % ahead) and loses every stride-2
 # one by 1.5-2.3x (the 1x1 stride-2 shortcuts write three zero pixels out of four through the full tile machinery).  Hence
 #   "tuned" (default): 1x1 stride 1 -> HIP forward + HIP data gradient; 3x3 up to 256 channels -> HIP forward (ahead of the library
-#                      by 2-8 % since the one-stage tile variant, plus the statistics pass it saves) and, at stride 1, HIP data
-#                      gradient; the 512-channel 3x3 layers and the stride-2 data gradients -> library; stride-2 1x1 shortcuts run
-#                      on the subsampled input as stride-1 pointwise layers (_Bottleneck.forward)
+#                      by 2-8 % since the one-stage tile variant, plus the statistics pass it saves); every 3x3 -> HIP data gradient
+#                      (the library's, for the 512-channel and the stride-2 layers, accumulates with atomics and differs from
+#                      run to run, and the trunk's backward carries that down to every gradient below it; the whole step shows
+#                      no difference in time); the 512-channel
+#                      3x3 forwards -> library; stride-2 1x1 shortcuts run on the subsampled input as stride-1 pointwise layers
+#                      (_Bottleneck.forward)
 #   "hipwgrad": library forward and data gradient everywhere (round 2's default); "lib": the library for everything;
 #   "hip3x3" / "hip" / "hip3x3+hipwgrad": the 3x3 / all / 3x3-only layers entirely on the HIP kernels (round-2 experiments:
 #   34.65 / 35.28 / 34.0-34.3 ms per `full` step against 33.7-33.8 for "hipwgrad")
@@ -54,10 +57,10 @@ def _resnet_conv(cin, cout, k, stride=1, padding=0, bias=False):
         m = Conv2dHipWgrad(cin, cout, k, stride=stride, padding=padding, bias=bias)
         if stride == 1 and k == 1:
             m.fwd = m.dgrad = "hip"
-        elif k == 3 and cin <= 256:
-            m.fwd = "hip"
-            if stride == 1:
-                m.dgrad = "hip"
+        elif k == 3:
+            m.dgrad = "hip"
+            if cin <= 256:
+                m.fwd = "hip"
         elif k == 1:
             m.cache_wt = True   # stride-2 shortcut: run on the subsampled input by _Bottleneck (forward_unstrided)
         return m
@@ -564,7 +567,10 @@ class BEVFusionHead(nn.Module):
         heatmap = (heatmap * (heatmap == local_max)).reshape(B, heatmap.shape[1], -1)
         top = heatmap.reshape(B, -1).topk(self.num_proposals, dim=-1).indices  # = argsort(descending)[:num_proposals]
         top_class, top_index = top // heatmap.shape[-1], top % heatmap.shape[-1]
-        query_feat = flat.gather(index=top_index[:, None, :].expand(-1, flat.shape[1], -1), dim=-1)
+        # the BEV rows at the proposals by indexing, not gather: two classes can pick the same cell, and gather's backward adds their
+        # gradients with atomics (a different sum from run to run); indexing's backward is a sorted, fixed-order accumulation
+        rows = flat.transpose(1, 2)[torch.arange(B, device=flat.device)[:, None], top_index]   # [B, P, C]
+        query_feat = rows.transpose(1, 2).contiguous()
         one_hot = F.one_hot(top_class, num_classes=self.num_classes)   # [B, P, classes]
         if _HEAD_ROWS and query_feat.is_cuda and self.class_encoding.kernel_size == (1,):
             # the k = 1 Conv1d over [B, classes, P] is a GEMM over the rows [B, P, classes]

@@ -61,6 +61,30 @@ def test_single_rank_json_contract(tmp_path):
     assert out["n_gpus"] == 1 and out["vs_baseline"] is None
 
 
+def test_dump_outputs_repeat_and_full_adds_figures(tmp_path):
+    """--dump-outputs: two runs with the same arguments write the same arrays (float32 / float64, at most 64 MB), and the last
+    timed step starts from the state the workload was built with (this workload has no dropout: it repeats the first step's
+    loss).  A plain line carries no per-op figures; --full adds them."""
+    import numpy as np
+    lines, dumps = [], []
+    for i, extra in enumerate(([], [], ["--full"])):
+        d = tmp_path / ("out%d" % i)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "dist_selftest", "--backend", "gloo",
+                            "--steps", "3", "--warmup", "2", "--batch", "2", "--dump-outputs", str(d), *extra],
+                           capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines.append(json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0]))
+        dumps.append({f: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))})
+    assert {"loss.npy", "grads.npy", "params.npy"} <= set(dumps[0])
+    assert all(a.dtype in (np.float32, np.float64) for a in dumps[0].values())
+    assert sum(a.nbytes for a in dumps[0].values()) <= 64 << 20
+    for dump in dumps[1:]:
+        assert dump.keys() == dumps[0].keys() and all(np.array_equal(dump[f], dumps[0][f]) for f in dump)
+    cfg = lines[0]["config"]
+    assert cfg["loss_last_step"] == cfg["loss_first_step"] and float(dumps[0]["loss.npy"]) > 0
+    assert not {"roofline", "roofline_ops", "ops"} & set(lines[0]) and {"roofline", "roofline_ops", "ops"} <= set(lines[2])
+
+
 def test_flat_grad_allreduce_handles_missing_grads_single_process(tmp_path):
     """FlatGradAllReduce on a 1-rank gloo group: gradients survive the round trip unchanged, a parameter without a gradient
     gets zeros, mixed dtypes go through separate flat buffers."""

@@ -397,3 +397,49 @@ def test_prediction_heads_as_row_gemms_match_the_conv1d_stacks(dev, monkeypatch,
     for (n, ba), (_, bb) in zip(a.named_buffers(), b.named_buffers()):
         if "num_batches" not in n:
             assert torch.allclose(ba, bb, rtol=1e-2 if amp else 1e-4, atol=1e-3 if amp else 1e-6), n
+
+
+def test_bench_restored_step_repeats():
+    """bench.py --dump-outputs restores the state the workload was built with before its last timed step (_InitialState:
+    parameters and buffers, MasterWeightAdamW's fp32 masters, moments and device step counter behind its flat tables, the
+    transposed weight copies, random number generators, dropout seeds).  Two restored steps of the benchmarked workload, after
+    different numbers of training steps, give the same loss and the same gradients: the backward sums in a fixed order (the
+    head's proposal rows, the ResNet-50 data gradients).  Only the weight gradients of the layers whose weight gradient is the
+    library's may differ, in the last bits of their fp32 sums; the weights after the step may differ where those gradients'
+    signs do, by up to two AdamW steps (lr 2e-4)."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+    code = """
+import sys, torch
+sys.path.insert(0, %r)
+import bench
+LIB = {"img_backbone.conv1.weight", "view_transform.dtransform.3.weight", "view_transform.depthnet.6.weight",
+       "pts_neck.deblocks.1.0.weight", "bbox_head.heatmap_head.1.weight"}
+wl = bench.FullModel(torch.device("cuda:0"), 4, 40000)
+init = bench._InitialState(wl.model, wl.opt)
+runs = []
+for r in range(2):
+    for _ in range(2 + r):
+        wl.step()
+    init.restore()
+    loss = wl.step()
+    torch.cuda.synchronize()
+    runs.append((float(loss), {n: (p.grad.detach().float().cpu(), p.detach().float().cpu())
+                               for n, p in wl.model.named_parameters() if p.grad is not None}))
+(l0, a), (l1, b) = runs
+assert l0 == l1, (l0, l1)
+assert a.keys() == b.keys() and len(a) > 300, (len(a), len(b))
+for n in a:
+    (ga, pa), (gb, pb) = a[n], b[n]
+    if n in LIB:   # an fp32 sum in another order, rounded to the gradient's dtype (bf16: up to one ulp of the element)
+        assert ((ga - gb).abs() <= 2 ** -7 * gb.abs() + 1e-3 * gb.abs().max()).all(), n
+        assert torch.allclose(pa, pb, rtol=2 ** -7, atol=4.5e-4), n
+    else:
+        assert torch.equal(ga, gb), n
+        assert (pa - pb).abs().max() <= 1e-6, n
+print("RESTORED_STEP_OK", l0)
+""" % root
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600, cwd=root)
+    assert r.returncode == 0 and "RESTORED_STEP_OK" in r.stdout, (r.stdout[-2000:], r.stderr[-4000:])

@@ -7,7 +7,8 @@ set -u
 n=${1:-2}; shift || true
 O=$PWD/gpurun_out/ab; mkdir -p $O
 one() { # dir tag
-  ( cd $1 && BENCH_REFERENCE_NUMERICS=0 BENCH_ISOLATED_STEPS=0 timeout -k 10 240 python3 bench.py --steps 20 --warmup 6 --no-cpu-baseline "${@:3}" > $O/$2.json 2> $O/$2.err ) || { tail -5 $O/$2.err; return 1; }
+  full=$(grep -q -- '"--full"' $1/bench.py && echo --full)   # the per-op figures printed below; a tree older than the option prints them anyway
+  ( cd $1 && BENCH_REFERENCE_NUMERICS=0 BENCH_ISOLATED_STEPS=0 timeout -k 10 240 python3 bench.py $full --steps 20 --warmup 6 --no-cpu-baseline "${@:3}" > $O/$2.json 2> $O/$2.err ) || { tail -5 $O/$2.err; return 1; }
   python3 - <<PY
 import json
 d=json.loads(open('$O/$2.json').read().strip().splitlines()[-1])

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Does the bench line reproduce from the kernel trace of the same run?
 
-    rocprofv3 --kernel-trace --stats --output-format csv -d D -o full -- python3 bench.py --steps K --warmup W --no-cpu-baseline > line.json
+    rocprofv3 --kernel-trace --stats --output-format csv -d D -o full -- python3 bench.py --full --steps K --warmup W --no-cpu-baseline > line.json
     python3 tools/check_roofline_vs_trace.py line.json D/.../full_kernel_trace.csv > profiles/rNN_roofline_vs_trace.txt
 
 For every entry of `roofline_ops` the per-step time bench.py printed (HIP events of the library around the op: `kernel_ms_per_step`

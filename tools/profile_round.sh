@@ -7,20 +7,20 @@ O=gpurun_out/rnd; mkdir -p $O
 part=${1:-A}
 run() { echo "== $*" >&2; "$@"; }
 if [ "$part" = A ]; then
-  run timeout -k 10 300 python3 bench.py > $O/bench_full.json 2> $O/bench_full.err || exit 1
+  run timeout -k 10 300 python3 bench.py --full > $O/bench_full.json 2> $O/bench_full.err || exit 1
   for w in lidar_only lidar_branch camera_only hotpath_v1; do
-    run timeout -k 10 200 python3 bench.py --workload $w --no-cpu-baseline > $O/bench_$w.json 2> $O/bench_$w.err || exit 1
+    run timeout -k 10 200 python3 bench.py --full --workload $w --no-cpu-baseline > $O/bench_$w.json 2> $O/bench_$w.err || exit 1
   done
-  run timeout -k 10 200 python3 bench.py --points 250000 --no-cpu-baseline > $O/bench_full_250k_points.json 2> $O/bench_250k.err || exit 1
-  run timeout -k 10 200 python3 bench.py --vt-fp32 --no-cpu-baseline > $O/bench_full_vt_fp32.json 2> $O/bench_vt.err || exit 1
-  BENCH_GRAPH=1 run timeout -k 10 200 python3 bench.py --no-cpu-baseline > $O/bench_full_graph.json 2> $O/bench_graph.err || exit 1
-  BFHIP_SPCONV_SORT=0 run timeout -k 10 200 python3 bench.py --no-cpu-baseline > $O/bench_full_nosort.json 2> $O/bench_nosort.err || exit 1
+  run timeout -k 10 200 python3 bench.py --full --points 250000 --no-cpu-baseline > $O/bench_full_250k_points.json 2> $O/bench_250k.err || exit 1
+  run timeout -k 10 200 python3 bench.py --full --vt-fp32 --no-cpu-baseline > $O/bench_full_vt_fp32.json 2> $O/bench_vt.err || exit 1
+  BENCH_GRAPH=1 run timeout -k 10 200 python3 bench.py --full --no-cpu-baseline > $O/bench_full_graph.json 2> $O/bench_graph.err || exit 1
+  BFHIP_SPCONV_SORT=0 run timeout -k 10 200 python3 bench.py --full --no-cpu-baseline > $O/bench_full_nosort.json 2> $O/bench_nosort.err || exit 1
 elif [ "$part" = B ]; then
   export BENCH_REFERENCE_NUMERICS=0
   export BENCH_PREWARM_STEPS=0   # the trace tools count optimizer steps: exactly warm-up + timed + one-queue steps
   # the same command without the tracer first: its figures are what the kernel sums of the trace are held against
-  run timeout -k 10 300 python3 bench.py --steps 10 --warmup 4 --no-cpu-baseline > $O/bench_full_plain_same_box.json 2> $O/plain.err || exit 1
-  run timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_full -o full -- python3 bench.py --steps 10 --warmup 4 --no-cpu-baseline > $O/bench_full_under_rocprof.json 2> $O/prof_full.err || exit 1
+  run timeout -k 10 300 python3 bench.py --full --steps 10 --warmup 4 --no-cpu-baseline > $O/bench_full_plain_same_box.json 2> $O/plain.err || exit 1
+  run timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_full -o full -- python3 bench.py --full --steps 10 --warmup 4 --no-cpu-baseline > $O/bench_full_under_rocprof.json 2> $O/prof_full.err || exit 1
   T=$(find $O/prof_full -name 'full_kernel_trace.csv' | head -1); S=$(find $O/prof_full -name 'full_kernel_stats.csv' | head -1)
   cp $S $O/bench_full_kernel_stats.csv
   python3 tools/trace_step.py $T 60 -6 > $O/bench_full_last_step_breakdown.txt   # last TIMED step (5 one-queue steps follow it)

@@ -28,7 +28,7 @@ def category(n):
 
 
 def main(path, top=45, which=-1):
-    """which: optimizer step to summarise, counted from the end (-1 = last; bench.py appends BENCH_ISOLATED_STEPS one-queue
+    """which: optimizer step to summarise, counted from the end (-1 = last; bench.py --full appends BENCH_ISOLATED_STEPS one-queue
     steps behind the timed region, so the last TIMED step is -(isolated + 1))."""
     rows = list(csv.DictReader(open(path)))
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
