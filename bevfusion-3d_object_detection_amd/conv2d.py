@@ -79,7 +79,7 @@ def wgrad_join():
 # Grouped weight gradients (default on, BFHIP_WGRAD_GROUPED=0 / conv2d.WGRAD_GROUPED = False: every layer launches its own):
 # inside a backward pass `_launch_wgrad` only COLLECTS (x, dy, weight) and returns no gradient; a callback queued on the autograd
 # engine runs when the pass ends (before `backward()` returns, on the caller's streams) and computes dW of all collected layers
-# with one launch per tile shape plus one slab-sum launch (csrc/conv2d.hip: conv_wgrad_group_kernel), then stores / accumulates
+# with one launch per tile shape plus one slab-sum launch (csrc/conv2d_wgrad.hip: conv_wgrad_group_kernel), then stores / accumulates
 # `weight.grad` itself -- what AccumulateGrad would have done.  Consequences: x and dy of every layer live until the end of the
 # pass (a few GB at batch 4 beside 288 GB of HBM); a weight with tensor hooks keeps the per-layer launch; so does a pass with an
 # explicit input list (`torch.autograd.grad(..., inputs)`, `backward(inputs=...)`: the engine captures those gradients from the
@@ -408,7 +408,7 @@ def _lib_dgrad(dy, x, weight, stride, pad, dil):
 
 
 class _LibConvHipWgradFunction(torch.autograd.Function):
-    """Forward and data gradient by the library convolution (MIOpen / CK through torch), weight gradient by csrc/conv2d.hip:
+    """Forward and data gradient by the library convolution (MIOpen / CK through torch), weight gradient by csrc/conv2d_wgrad.hip:
     for layers where the library's forward is ahead (ResNet-50's 1x1 and 3x3 convolutions) but its weight gradient brings an
     fp32 zero-fill and a cast launch per call (atomic split-K) and is no faster than the HIP one."""
 
@@ -622,7 +622,7 @@ def conv2d(x, weight, bias=None, stride=1, padding=0, dilation=1, emit_stats=Fal
 
 
 def lib_conv2d(x, weight, stride, padding, dilation, dgrad_hip=False):
-    """Library forward (and data gradient unless `dgrad_hip`), weight gradient on csrc/conv2d.hip (_LibConvHipWgradFunction)."""
+    """Library forward (and data gradient unless `dgrad_hip`), weight gradient on csrc/conv2d_wgrad.hip (_LibConvHipWgradFunction)."""
     ext = _conv_ext() if x.is_cuda and x.dim() == 4 and not weight._backward_hooks else None
     if ext is not None:
         return ext.lib_conv2d(x, weight, int(stride), int(padding), int(dilation), bool(dgrad_hip),
@@ -687,7 +687,7 @@ class Conv2d(nn.Conv2d):
 
 
 class Conv2dHipWgrad(Conv2d):
-    """nn.Conv2d (bias-free) whose weight gradient always runs on csrc/conv2d.hip and whose forward / data gradient take the
+    """nn.Conv2d (bias-free) whose weight gradient always runs on csrc/conv2d_wgrad.hip and whose forward / data gradient take the
     library (MIOpen / CK through torch) or the HIP kernel, each on its own (`fwd`, `dgrad`: "lib" | "hip"; default: both on the
     library): for layers where one side's kernel is ahead in one direction only (dense_modules.ResNet50).  A HIP forward
     emits the BatchNorm statistics like `Conv2d`.  Falls back to nn.Conv2d when the call is not one the HIP kernels serve."""

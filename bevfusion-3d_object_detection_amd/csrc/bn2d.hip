@@ -549,7 +549,7 @@ constexpr int kSlabInts = 16384;  // >= CT * (1 + ng) = 256 * 33
 constexpr int kSlabs = 32;
 
 inline bool fold_enabled() {
-  static const bool on = [] { const char *e = getenv("BFHIP_BN2D_FOLD"); return e && e[0] == '1'; }();
+  static const bool on = [] { const char *e = env_str("BFHIP_BN2D_FOLD"); return e && e[0] == '1'; }();
   return on;
 }
 

@@ -13,6 +13,17 @@ void set_error(const char *fmt, ...) {
   va_end(ap);
 }
 
+int device_cus() {
+  static std::atomic<int> cached[kMaxDevices];  // 0 = not asked yet
+  int dev = 0, v = 0;
+  if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return 256; }
+  const bool slot = dev >= 0 && dev < kMaxDevices;
+  if (slot && (v = cached[dev].load(std::memory_order_relaxed)) > 0) return v;
+  if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) { (void)hipGetLastError(); return 256; }
+  if (slot) cached[dev].store(v, std::memory_order_relaxed);
+  return v;
+}
+
 // ---- profiler: HIP events recorded on the SAME stream as the kernel, around the dominant
 // kernel of each op only (not around memsets / helper launches).
 static int g_prof_on = 0;
@@ -21,8 +32,6 @@ static std::vector<Pending> g_pending[BFHIP_OP_COUNT];
 static double g_sum_ms[BFHIP_OP_COUNT];
 static long long g_count[BFHIP_OP_COUNT];
 static std::mutex g_mu;
-
-bool prof_enabled() { return g_prof_on != 0; }
 
 void prof_begin(int op, hipStream_t s, ProfScope *sc) {
   sc->active = false;

@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <stdlib.h>
+#include <atomic>
 
 #include "../../include/bevfusion_hip.h"
 
@@ -26,7 +28,6 @@ inline int check_launch(const char *what) {
 
 // optional profiler (capi.hip): events on the op's stream around its dominant kernel
 struct ProfScope { bool active; int op; hipStream_t stream; hipEvent_t a, b; };
-bool prof_enabled();
 void prof_begin(int op, hipStream_t s, ProfScope *sc);
 void prof_end(ProfScope *sc);
 
@@ -63,8 +64,35 @@ __device__ __forceinline__ long long xcd_chunked_block(long long bid, long long 
   return base + slot;
 }
 
-// sparse weight gradient on the bf16 matrix cores (csrc/conv2d.hip: the transposing-LDS-read machinery of the dense conv
-// weight gradient with the rulebook as the gather); called by bfhip_spconv_wgrad for bf16 features
+// ---- tuning knobs: every BFHIP_* environment variable is read through these (callers keep the value in a function-local static)
+inline const char *env_str(const char *name) { return getenv(name); }  // nullptr when unset (all that some knobs test)
+inline int env_int(const char *name, int dflt) { const char *e = env_str(name); return e ? atoi(e) : dflt; }
+inline long long env_ll(const char *name, long long dflt) { const char *e = env_str(name); return e ? atoll(e) : dflt; }
+// knobs for which 0 (or anything not positive) means "use the default"
+inline int env_pos_int(const char *name, int dflt) { const int v = env_int(name, 0); return v > 0 ? v : dflt; }
+
+constexpr int kMaxDevices = 64;  // device indices with a slot in the per-device caches below
+// compute units of the current device (capi.hip; cached per device index); 256 when no device answers -- the host-only tests
+// call the planners without a GPU
+int device_cus();
+
+// Launch of a kernel that needs more dynamic LDS than the default limit: raises the limit to `lds_limit` once per device (the
+// attribute belongs to the (kernel, device) pair, so the state is a flag per device index; racing threads at worst both set the
+// same value), then launches.  Costs one hipGetDevice per launch.
+template <auto Kernel, typename... Args>
+inline void launch_big_lds(int lds_limit, dim3 grid, dim3 block, size_t lds, hipStream_t s, Args... args) {
+  static std::atomic<bool> done[kMaxDevices];
+  int dev = 0;
+  const bool slot = hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < kMaxDevices;
+  if (!slot || !done[dev].load(std::memory_order_acquire)) {
+    (void)hipFuncSetAttribute((const void *)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_limit);
+    if (slot) done[dev].store(true, std::memory_order_release);
+  }
+  hipLaunchKernelGGL(Kernel, grid, block, lds, s, args...);
+}
+
+// sparse weight gradient on the bf16 matrix cores (csrc/spconv_wgrad_tr.hip: the transposing-LDS-read machinery of the dense conv
+// weight gradient, csrc/wgrad_tr.h, with the rulebook as the gather); called by bfhip_spconv_wgrad for bf16 features
 size_t spconv_wgrad_tr_workspace_bytes(int KV, int Cin, int Cout, int n_rows);
 bool spconv_wgrad_tr_supported(int KV, int Cin, int Cout);
 int spconv_wgrad_tr(const void *in, const void *dout, const int32_t *pairs, int ld, int KV, int n_rows, int Cin, int Cout,

@@ -671,13 +671,8 @@ BFHIP_EXPORT int bfhip_hungarian(const float *cost, const int32_t *n_gt, int B, 
     stage_cap = P * G;
     lds += (size_t)P * G * sizeof(float);
   }
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void *)hungarian_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(hungarian_kernel, dim3(B), dim3(64), lds, (hipStream_t)stream, cost, n_gt, P, G, M, assigned,
-                     status, stage_cap);
+  launch_big_lds<hungarian_kernel>(150 * 1024, dim3(B), dim3(64), lds, (hipStream_t)stream, cost, n_gt, P, G, M, assigned, status,
+                                   stage_cap);
   return check_launch("hungarian");
 }
 

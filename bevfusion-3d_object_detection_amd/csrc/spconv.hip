@@ -1647,7 +1647,7 @@ __global__ __launch_bounds__(kSortThreads) void sort_rows_chunk_kernel(const uns
 }
 
 hipError_t SortScratch::sort(int n_rows, int KV, int32_t *perm, hipStream_t stream) {
-  static const int chunked = [] { const char *e = getenv("BFHIP_SPCONV_CHUNK_SORT"); return e ? atoi(e) : 1; }();
+  static const int chunked = env_int("BFHIP_SPCONV_CHUNK_SORT", 1);
   if (chunked && KV <= 30) {
     hipLaunchKernelGGL(sort_rows_chunk_kernel, dim3(ceil_div(n_rows, kSortChunk)), dim3(kSortThreads), 0, stream, keys, n_rows, KV,
                        perm);
@@ -2049,15 +2049,6 @@ static inline int wgrad_splits(int KV, int GI, int GJ, int n_rows) {
 }
 
 // ---- geometry of the row-streamed kernel (see spconv_wgrad64p_kernel)
-static int device_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) n = v;
-    else { (void)hipGetLastError(); n = 256; }
-  }
-  return n;
-}
 constexpr int kSkMaxBlocksPerCu = 4;
 template <int R, bool IO16>
 static int wgrad_sk_resident_blocks() {  // workgroups the chip holds at once: the grid of the streamed kernel
@@ -2068,8 +2059,7 @@ static int wgrad_sk_resident_blocks() {  // workgroups the chip holds at once: t
       (void)hipGetLastError();
       occ = 2;
     }
-    const char *e = getenv("BFHIP_WGRAD_BLOCKS_PER_CU");  // tuning knob (tools/wgrad_trace.py)
-    if (e && atoi(e) > 0) occ = atoi(e);
+    occ = env_pos_int("BFHIP_WGRAD_BLOCKS_PER_CU", occ);  // tuning knob (tools/wgrad_trace.py)
     if (occ > kSkMaxBlocksPerCu) occ = kSkMaxBlocksPerCu;
     p = occ * device_cus();
   }
@@ -2108,7 +2098,7 @@ BFHIP_EXPORT int bfhip_spconv_wgrad(const void *in, const void *dout, const int3
   float *partial = (float *)workspace;
   ProfScope ps, ps_op;
   prof_begin(BFHIP_OP_SPCONV_WGRAD, stream, &ps_op);  // the whole op: counts + main + reduce
-  static const int use_tr = getenv("BFHIP_SPCONV_WGRAD_FP32MFMA") ? 0 : 1;
+  static const int use_tr = env_str("BFHIP_SPCONV_WGRAD_FP32MFMA") ? 0 : 1;
   if (io_bf16 && use_tr && !perm && spconv_wgrad_tr_supported(KV, Cin, Cout)) {
     // bf16 features: the bf16-MFMA kernel (16x the matrix rate of the fp32-MFMA kernels below)
     // (the BFHIP_OP_SPCONV_WGRAD_MAIN scope brackets the main kernel only, inside spconv_wgrad_tr: round 2 had it around the

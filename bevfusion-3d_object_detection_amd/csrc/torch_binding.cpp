@@ -475,7 +475,7 @@ tensor_list conv2d(const Tensor &x, const Tensor &weight, const c10::optional<Te
   return ConvFn::apply(x, weight, bias, stride, pad, dil, emit_stats, dgrad_lib, fork, wt);
 }
 
-// conv2d.py::_LibConvHipWgradFunction: forward (and by default the data gradient) by the library, weight gradient on csrc/conv2d.hip
+// conv2d.py::_LibConvHipWgradFunction: forward (and by default the data gradient) by the library, weight gradient on csrc/conv2d_wgrad.hip
 class LibConvFn : public torch::autograd::Function<LibConvFn> {
  public:
   static Tensor forward(AutogradContext *ctx, const Tensor &x_, const Tensor &weight, int64_t stride, int64_t pad, int64_t dil,

@@ -30,7 +30,7 @@ from .registry import MODELS
 
 
 # ----------------------------------------------------------------------------- image backbone
-# Which kernels the ResNet-50 trunk's 52 convolutions take (BFHIP_RESNET_CONV).  The weight gradient is csrc/conv2d.hip's in
+# Which kernels the ResNet-50 trunk's 52 convolutions take (BFHIP_RESNET_CONV).  The weight gradient is csrc/conv2d_wgrad.hip's in
 # every mode but "lib" (the library's brings an fp32 zero-fill and a cast launch per call and is no faster).  Forward and data
 # gradient, GPU time per call from `tools/resnet_conv_micro.py` (graph replay, batch 24 x 64 x 176 after the stem; sums over the
 # trunk): library forward 1.72 ms, HIP 1.96 ms -- but a HIP forward hands the BatchNorm behind it its statistics (0.34 ms of

@@ -16,7 +16,7 @@ _DT = {torch.float32: 0, torch.bfloat16: 1}
 _WS = {}
 
 
-# bf16 operands: x^T y over K rows IS the weight gradient of a 1x1 convolution over a [1, K, 1, C] map, and csrc/conv2d.hip's
+# bf16 operands: x^T y over K rows IS the weight gradient of a 1x1 convolution over a [1, K, 1, C] map, and csrc/conv2d_wgrad.hip's
 # weight-gradient kernel (bf16 MFMA, LDS-DMA ring, split over the rows) does it in about a third of the time of csrc/xty.hip's
 # fp32-MFMA kernel (K = 129 600, 128 x 128: ~30 vs 90 us).  BFHIP_XTY_CONV=0: always csrc/xty.hip.
 XTY_CONV = os.environ.get("BFHIP_XTY_CONV", "1") == "1"

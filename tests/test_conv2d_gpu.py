@@ -99,7 +99,7 @@ def test_forward_backward_vs_torch_cpu(dev, g):
                          ids=lambda g: "x".join(str(v) for v in g[:9]))
 @pytest.mark.parametrize("fwd,dgrad", [("lib", "lib"), ("lib", "hip"), ("hip", "hip"), ("hip", "lib")])
 def test_library_forward_hip_wgrad_hybrid(dev, g, fwd, dgrad):
-    """Conv2dHipWgrad (the ResNet-50 trunk's convolutions): weight gradient by csrc/conv2d.hip, forward and data gradient each
+    """Conv2dHipWgrad (the ResNet-50 trunk's convolutions): weight gradient by csrc/conv2d_wgrad.hip, forward and data gradient each
     by the library or the HIP kernel (dense_modules picks per layer); same tolerances as the all-HIP path against torch on the
     CPU in fp32.  A HIP forward must also hand over its BatchNorm statistics."""
     from bevfusion_amd.conv2d import Conv2dHipWgrad
@@ -290,7 +290,7 @@ def _wgrad_stack(dev, dtype):
 @pytest.mark.parametrize("front", ["python", "ext"])
 @pytest.mark.parametrize("wdtype", [torch.bfloat16, torch.float32])
 def test_grouped_weight_gradients_match_the_in_line_launches(dev, monkeypatch, wdtype, front):
-    """conv2d.WGRAD_GROUPED (csrc/conv2d.hip: conv_wgrad_group_kernel): dW of all layers of a backward pass in one launch per tile
+    """conv2d.WGRAD_GROUPED (csrc/conv2d_wgrad.hip: conv_wgrad_group_kernel): dW of all layers of a backward pass in one launch per tile
     shape at the end of the pass equals the per-layer launches up to the fp32 summation order (the pixel range is cut into a
     different number of splits: <= 1e-5 rel on fp32 dW, one bf16 rounding on bf16 dW); the gradients are in place when
     backward() returns, a second pass without clearing .grad accumulates, and the result is deterministic."""

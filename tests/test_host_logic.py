@@ -92,7 +92,7 @@ def test_head_and_neck_state_dict_keys_follow_the_reference_names():
 
 
 def test_grouped_weight_gradient_plan_is_a_partition():
-    """bfhip_conv2d_wgrad_group_plan (host only, csrc/conv2d.hip): the table it writes for the 77 dense layers of the `full` workload's
+    """bfhip_conv2d_wgrad_group_plan (host only, csrc/conv2d_wgrad.hip): the table it writes for the 77 dense layers of the `full` workload's
     backward pass (shapes of profiles/r03_conv_wgrad_layers.txt) cuts every layer's pixel range into splits that cover it exactly
     once, gives every layer its own slab range, lists the workgroups of each tile shape once, and hands the 8 XCDs consecutive
     chunks of (nearly) equal total steps.  The item layout below mirrors `struct WgradItem` (internal; test in lock-step)."""

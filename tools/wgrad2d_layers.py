@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per distinct convolution shape of the `full` workload (batch 4): time of the dense weight gradient (csrc/conv2d.hip,
+"""Per distinct convolution shape of the `full` workload (batch 4): time of the dense weight gradient (csrc/conv2d_wgrad.hip,
 bfhip_conv2d_wgrad: main kernel + slab sum) from the library's own HIP-event scope, TFLOP/s, and its share of the step."""
 import collections
 import json
