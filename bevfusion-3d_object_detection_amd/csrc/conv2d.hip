@@ -690,6 +690,13 @@ int launch_igemm(const void *x, const void *wt, const float *bias, void *y, floa
   return check_launch(what);
 }
 
+// geometry of the data gradient as the launch sees it: BFHIP_CONV_DGRAD_PARITY=0 keeps strided layers on the plain transposed
+// gather (MODE 1) instead of the parity classes (MODE 2).  One function for the launch and for bfhip_conv2d_launch_choice
+ConvGeom dgrad_geom(int N, int H, int W, int Cin, int ldx, int Cout, int ldg, int KH, int KW, int stride, int pad, int dil) {
+  static const int parity = env_int("BFHIP_CONV_DGRAD_PARITY", 1);
+  return conv_geom_dgrad(N, H, W, Cin, ldx, Cout, ldg, KH, KW, stride, pad, dil, parity != 0);
+}
+
 }  // namespace
 }  // namespace bfhip
 
@@ -721,6 +728,22 @@ BFHIP_EXPORT int bfhip_conv2d_fwd(const void *x, int ldx, const void *w, const f
   return rc;
 }
 
+// Which kernel bfhip_conv2d_fwd (dir 0) / bfhip_conv2d_dgrad(_wt) (dir 1) would launch for this geometry in this process (knobs
+// and CU count included): the geometry builders and choose_igemm of the launch path, no launch, no device needed.
+// out_host[8] = {pointwise, shape (pointwise: BN), stages, gather mode (ConvGeom::transposed), BM, BN, tiles_m, tiles_n}
+BFHIP_EXPORT int bfhip_conv2d_launch_choice(int dir, int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad,
+                                            int dil, int out_f32, int32_t *out_host) {
+  BFHIP_REQUIRE(out_host && (dir == 0 || dir == 1), "conv2d_launch_choice: bad arguments");
+  BFHIP_REQUIRE(bfhip_conv2d_supported(N, H, W, Cin, Cout, KH, KW, stride, pad, dil), "conv2d_launch_choice: unsupported geometry");
+  const ConvGeom g = dir ? dgrad_geom(N, H, W, Cin, Cin, Cout, Cout, KH, KW, stride, pad, dil)
+                         : conv_geom_fwd(N, H, W, Cin, Cin, Cout, KH, KW, stride, pad, dil, Cout);
+  BFHIP_REQUIRE((dir ? g.H > 0 && g.W > 0 : g.OH > 0 && g.OW > 0), "conv2d_launch_choice: empty output");
+  const IgemmChoice c = choose_igemm(g, out_f32, device_cus());
+  const int32_t v[8] = {c.pointwise ? 1 : 0, c.pointwise ? c.BN : c.shape, c.stages, g.transposed, c.BM, c.BN, c.tiles_m, c.tiles_n};
+  for (int i = 0; i < 8; ++i) out_host[i] = v[i];
+  return BFHIP_OK;
+}
+
 BFHIP_EXPORT size_t bfhip_conv2d_dgrad_workspace_bytes(int Cin, int Cout, int KH, int KW) {
   return align_up((size_t)Cin * KH * KW * Cout * 2, 256);
 }
@@ -735,8 +758,7 @@ static int conv2d_dgrad_impl(const void *dy, int ldg, const void *w, void *dx, i
   BFHIP_REQUIRE(dy && dx && workspace, "conv2d_dgrad: null pointer");
   BFHIP_REQUIRE(workspace_bytes >= bfhip_conv2d_dgrad_workspace_bytes(Cin, Cout, KH, KW), "conv2d_dgrad: workspace too small");
   BFHIP_REQUIRE(dma_operand_ok(dy, ldg, Cout) && ((uintptr_t)workspace % 16) == 0 && ldx >= Cin, kOperandMsg, "conv2d_dgrad");
-  static const int parity = env_int("BFHIP_CONV_DGRAD_PARITY", 1);
-  const ConvGeom g = conv_geom_dgrad(N, H, W, Cin, ldx, Cout, ldg, KH, KW, stride, pad, dil, parity != 0);
+  const ConvGeom g = dgrad_geom(N, H, W, Cin, ldx, Cout, ldg, KH, KW, stride, pad, dil);
   BFHIP_REQUIRE((long long)N * g.H * g.W * ldg < (1LL << 31), "conv2d_dgrad: tensors of 2^31 elements or more are not supported");
   BFHIP_REQUIRE(((uintptr_t)addend % 4) == 0 && (addend_stride == 1 || addend_stride == 2), "conv2d_dgrad: bad addend");
   ProfScope ps;

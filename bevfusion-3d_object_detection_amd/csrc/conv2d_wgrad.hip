@@ -409,6 +409,20 @@ BFHIP_EXPORT size_t bfhip_conv2d_wgrad_workspace_bytes(int N, int OH, int OW, in
   return align_up((size_t)wg.splits * Cout * KH * KW * Cin * sizeof(float), 256);
 }
 
+// The plan bfhip_conv2d_wgrad would launch for this geometry in this process (wgrad_plan of the launch path; host only):
+// out_host[4] = {tile shape (wgrad_shape), tiles_co, tiles_k, splits}
+BFHIP_EXPORT int bfhip_conv2d_wgrad_choice(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int dil,
+                                           int32_t *out_host) {
+  BFHIP_REQUIRE(out_host, "conv2d_wgrad_choice: bad arguments");
+  BFHIP_REQUIRE(bfhip_conv2d_supported(N, H, W, Cin, Cout, KH, KW, stride, pad, dil), "conv2d_wgrad_choice: unsupported geometry");
+  const ConvGeom g = conv_geom_fwd(N, H, W, Cin, Cin, Cout, KH, KW, stride, pad, dil, 0);
+  BFHIP_REQUIRE(g.OH > 0 && g.OW > 0, "conv2d_wgrad_choice: empty output");
+  WgradGeom wg;
+  out_host[0] = wgrad_plan(g.M, (long long)g.OH * g.OW, Cout, KH * KW * Cin, wg);
+  out_host[1] = wg.tiles_co; out_host[2] = wg.tiles_k; out_host[3] = wg.splits;
+  return BFHIP_OK;
+}
+
 // dw[Cout][KH][KW][Cin] (fp32 or bf16) = sum over pixels of dy x gathered x
 BFHIP_EXPORT int bfhip_conv2d_wgrad(const void *x, int ldx, const void *dy, int ldg, void *dw, int N, int H, int W, int Cin,
                                     int Cout, int KH, int KW, int stride, int pad, int dil, int dw_bf16, void *workspace,

@@ -523,6 +523,15 @@ int bfhip_conv2d_weight_transpose_batched(const void *segs_dev, int nseg, long l
  * fp32 convolution (a*b ~ a_hi*b_hi + a_hi*b_lo + a_lo*b_hi on the bf16 matrix cores, fp32 accumulation): src f32 [P][C] dense ->
  * chan (optional) bf16 [P][3C] and batch (optional) bf16 [3][P][C]; bit k of order_* set = block k holds lo.  C % 8 == 0. */
 int bfhip_split_bf16x3(const float *src, long long P, int C, void *chan, int order_chan, void *batch, int order_batch, void *stream);
+/* Host-only queries of the launch decision (no launch, no device needed; the same functions, knobs and CU count as the launch
+ * path).  launch_choice: dir 0 = bfhip_conv2d_fwd, 1 = bfhip_conv2d_dgrad(_wt); out_host[8] = {pointwise kernel (0 | 1), tile shape
+ * (0 = 128x64, 1 = 128x128, 2 = 256x256; pointwise: the tile width), LDS stages, gather mode (0 forward, 1 transposed, 2 parity
+ * classes), tile rows, tile columns, row tiles, column tiles}.  wgrad_choice: out_host[4] = {tile shape (0 = 128x128, 1 = 128 co x
+ * 256 k, 2 = 256 co x 128 k), tiles along Cout, tiles along K, pixel-range splits}. */
+int bfhip_conv2d_launch_choice(int dir, int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int dil,
+                               int out_f32, int32_t *out_host);
+int bfhip_conv2d_wgrad_choice(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int dil,
+                              int32_t *out_host);
 size_t bfhip_conv2d_wgrad_workspace_bytes(int N, int OH, int OW, int Cin, int Cout, int KH, int KW);
 int bfhip_conv2d_wgrad(const void *x, int ldx, const void *dy, int ldg, void *dw, int N, int H, int W, int Cin, int Cout,
                        int KH, int KW, int stride, int pad, int dil, int dw_bf16, void *workspace, size_t workspace_bytes,
