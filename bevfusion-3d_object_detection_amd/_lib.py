@@ -128,6 +128,11 @@ SIGNATURES = {
     "bfhip_adamw_chunk_elems": (_c_int, []),
     "bfhip_adamw_step": (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp] + [ctypes.c_float] * 6 + [_c_vp]),
     "bfhip_query_losses": (_c_int, [_c_vp] * 7 + [_c_int] * 6 + [ctypes.c_float, ctypes.c_float] + [_c_vp] * 4),
+    "bfhip_swin_attn_supported": (_c_int, [_c_int] * 7),
+    "bfhip_swin_attn_parts": (_c_int, [_c_int] * 4),
+    "bfhip_swin_attn_fwd": (_c_int, [_c_vp, ctypes.c_longlong, _c_vp] + [_c_int] * 5 + [ctypes.c_float, _c_vp, _c_vp, _c_vp]),
+    "bfhip_swin_attn_bwd": (_c_int, [_c_vp, ctypes.c_longlong, _c_vp, _c_vp, _c_vp, _c_vp] + [_c_int] * 5 +
+                            [ctypes.c_float, _c_vp, _c_vp, _c_int, _c_vp]),
 }
 
 _lib = None

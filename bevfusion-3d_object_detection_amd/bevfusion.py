@@ -18,7 +18,7 @@ from . import _lib
 from .ops import Voxelization
 from .ops.voxel import voxel_layer
 from .registry import MODELS
-from . import dense_modules, depth_lss, sparse_encoder  # noqa: F401  (register the module names)
+from . import dense_modules, depth_lss, sparse_encoder, swin  # noqa: F401  (register the module names)
 
 
 def voxel_mean(voxels, num_points):
@@ -354,10 +354,12 @@ class BEVFusion(nn.Module):
         return loss, logged
 
 
-def nuscenes_config(camera=True, lidar=True):
+def nuscenes_config(camera=True, lidar=True, img_backbone="resnet50"):
     """Model dict of the reference's nuScenes configs
     (projects/BEVFusion/configs/nuscenes/bevfusion_lidar_voxel0075...py:44-131 and
-    bevfusion_lidar-cam_voxel0075...py:9-57) with BASELINE.json's ResNet-50 image backbone."""
+    bevfusion_lidar-cam_voxel0075...py:9-57) with BASELINE.json's ResNet-50 image backbone; img_backbone="swin_t": the
+    reference's own Swin-T backbone dict (swin.swin_t_config) and the matching neck input channels."""
+    assert img_backbone in ("resnet50", "swin_t"), img_backbone
     cfg = dict(
         type="BEVFusion",
         data_preprocessor=dict(voxelize_cfg=dict(max_num_points=10, point_cloud_range=[-54.0, -54.0, -5.0, 54.0, 54.0, 3.0],
@@ -406,6 +408,9 @@ def nuscenes_config(camera=True, lidar=True):
         cfg["view_transform"] = dict(type="DepthLSSTransform", in_channels=256, out_channels=80, image_size=[256, 704],
                                      feature_size=[32, 88], xbound=[-54.0, 54.0, 0.3], ybound=[-54.0, 54.0, 0.3],
                                      zbound=[-10.0, 10.0, 20.0], dbound=[1.0, 60.0, 0.5], downsample=2)
+        if img_backbone == "swin_t":
+            cfg["img_backbone"] = swin.swin_t_config()
+            cfg["img_neck"]["in_channels"] = [192, 384, 768]
     if camera and lidar:
         cfg["fusion_layer"] = dict(type="ConvFuser", in_channels=[80, 256], out_channels=256)
     elif camera:

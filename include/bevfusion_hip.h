@@ -593,6 +593,30 @@ int bfhip_adamw_step(const void *segs_dev, const int64_t *grad_ptrs_dev, const i
                      float *partial_dev, float *scalars_dev, float lr, float beta1, float beta2, float eps,
                      float weight_decay, float max_norm, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Shifted-window multi-head self-attention of the Swin image backbone (csrc/swin_attn.hip; the reference's camera configs build
+ *   img_backbone = mmdet.SwinTransformer, whose ShiftWindowMSA pads, rolls, partitions, masks and un-partitions through copies).
+ *   Window 7, head dim 32, bf16 with fp32 softmax statistics; roll, partition, bias, mask and softmax are inside the kernel.
+ *   qkv   bf16 [B, Hp, Wp, 3C] with token pitch qkv_pitch (elements, >= 3C, multiple of 8), C = heads * 32, channel =
+ *         which * C + head * 32 + d (which: 0 q, 1 k, 2 v) -- the qkv Linear's output as it is; Hp, Wp multiples of 7
+ *   bias  f32 [heads, 49, 49]: the relative-position table gathered to (query, key) pairs
+ *   shift 0 | 3: token (h, w) sits in the window of ((h - shift) mod Hp, (w - shift) mod Wp); with shift > 0 a -100 is added
+ *         where query and key lie in different regions ([0, L-7), [L-7, L-3), [L-3, L) of the shifted coordinate, per axis)
+ *   out   bf16 [B, Hp, Wp, C] dense; lse f32 [B, Hp, Wp, heads]
+ *   bwd   recomputes the probabilities from lse; dqkv bf16 [B, Hp, Wp, 3C] dense, every element written; dbias_partial f32
+ *         [parts, heads, 49, 49] with parts = bfhip_swin_attn_parts(): one slab per workgroup column, each summed in a fixed
+ *         order; the caller adds the slabs.  No floating-point atomics: forward and backward are run-to-run reproducible.
+ *   bfhip_swin_attn_supported / _parts are host-only (no device needed); supported answers 0 for any other window, head dim,
+ *   shift, or an Hp / Wp that is not a multiple of 7.
+ * --------------------------------------------------------------------------------------- */
+int bfhip_swin_attn_supported(int B, int Hp, int Wp, int heads, int window, int head_dim, int shift);
+int bfhip_swin_attn_parts(int B, int Hp, int Wp, int heads);
+int bfhip_swin_attn_fwd(const void *qkv, long long qkv_pitch, const float *bias, int B, int Hp, int Wp, int heads, int shift,
+                        float scale, void *out, float *lse, void *stream);
+int bfhip_swin_attn_bwd(const void *qkv, long long qkv_pitch, const float *bias, const void *out, const void *dout,
+                        const float *lse, int B, int Hp, int Wp, int heads, int shift, float scale, void *dqkv,
+                        float *dbias_partial, int parts, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
