@@ -1,5 +1,5 @@
 """Cross attention of a few queries over very many keys (csrc/attn.hip): the TransFusion decoder layer's 200 object
-queries against all 32 400 BEV cells (BF/transformer.py:60-105).  Same maths as torch's scaled_dot_product_attention
+queries (500 in the reference's custom_data configs) against all 32 400 BEV cells (BF/transformer.py:60-105).  Same maths as torch's scaled_dot_product_attention
 (softmax(Q K^T / sqrt(d)) with dropout on the weights, times V) in bf16 with fp32 softmax statistics; the key axis is split
 over the chip instead of the (tiny) query axis.  Inputs stay in the [B, L, H*16] layout the projections produce."""
 import itertools
@@ -11,15 +11,32 @@ import torch
 from . import _lib
 
 ENABLED = os.environ.get("BFHIP_SPLITK_ATTN", "1") == "1"
+WIDE = os.environ.get("BFHIP_SPLITK_ATTN_WIDE", "1") == "1"  # more than 256 queries on the kernels (0: library SDPA, for A/B runs)
 MIN_KEYS = 2048
 _WS = {}
 _calls = itertools.count(1)
 
 
-def supported(q, k, v, num_heads):
+def _eligible(q, k, v, num_heads):
     return (ENABLED and q.is_cuda and q.dtype == k.dtype == v.dtype == torch.bfloat16 and q.dim() == 3
-            and q.shape[2] == num_heads * 16 and q.shape[1] <= 256 and k.shape[1] >= MIN_KEYS and k.shape == v.shape
+            and q.shape[2] == num_heads * 16 and k.shape[1] >= MIN_KEYS and k.shape == v.shape
             and q.shape[0] == k.shape[0])
+
+
+def supported(q, k, v, num_heads):
+    """The single-block path: every query of a (batch, head) in one workgroup, at most 256 queries."""
+    return _eligible(q, k, v, num_heads) and q.shape[1] <= 256
+
+
+def max_queries():
+    """The largest Lq the C entry points accept (bfhip_attn_max_queries: 512)."""
+    return int(_lib.load().bfhip_attn_max_queries())
+
+
+def supported_wide(q, k, v, num_heads):
+    """The same conditions for 256 < Lq <= max_queries() (the custom_data head's 500 proposals): query-block grid axis in the
+    forward, 32 query tiles per key tile in the backward."""
+    return WIDE and _eligible(q, k, v, num_heads) and 256 < q.shape[1] <= max_queries()
 
 
 def _workspace(t, nbytes, stream):
@@ -94,7 +111,7 @@ class _CrossAttention(torch.autograd.Function):
 
 
 def cross_attention(q, k, v, num_heads, dropout_p=0.0, seed=None):
-    """q [B, Lq, H*16], k / v [B, Lk, H*16] (bf16) -> [B, Lq, H*16]; heads are channel groups of 16."""
+    """q [B, Lq, H*16], k / v [B, Lk, H*16] (bf16) -> [B, Lq, H*16]; heads are channel groups of 16; Lq <= max_queries()."""
     if dropout_p > 0.0 and seed is None:
         seed = next_seed()
     return _CrossAttention.apply(q, k, v, num_heads, float(dropout_p), int(seed or 0))

@@ -418,6 +418,43 @@ def nuscenes_config(camera=True, lidar=True, img_backbone="resnet50"):
     return cfg
 
 
+CUSTOM_CLASSES = ("car", "truck", "bus", "bicycle", "pedestrian")
+
+
+def custom_data_config(camera=True, lidar=True):
+    """Model dict of the reference's own `custom_data` configs, merged the way mmengine resolves `_base_`
+    (projects/BEVFusion/configs/custom_data/lidar_custom.py:38-146 and lidar-cam_custom.py:9-59): five cameras of 384 x 704
+    pixels (48 x 88 feature maps), three point features, the five CUSTOM_CLASSES, 500 proposals, velocity code weights 0 and
+    the Swin-T image backbone.  tests/golden/custom_data_model_cfg.json holds the reference's merged dict; the keys left out
+    here (norm / act / conv cfgs our modules fix, init_cfg, the data preprocessor's mean / std, unused type names) are
+    listed in tests/test_custom_config_cpu.py."""
+    cfg = nuscenes_config(camera=camera, lidar=lidar, img_backbone="swin_t")
+    cfg["data_preprocessor"]["pad_size_divisor"] = 32
+    cfg["pts_voxel_encoder"] = dict(type="HardSimpleVFE", num_features=3)
+    head = cfg["bbox_head"]
+    head["num_proposals"] = 500
+    head["num_classes"] = len(CUSTOM_CLASSES)
+    head["train_cfg"]["code_weights"] = [1.0] * 8 + [0.0, 0.0]
+    if lidar:
+        cfg["pts_middle_encoder"]["in_channels"] = 3
+    if camera:
+        cfg["data_preprocessor"]["bgr_to_rgb"] = False
+        cfg["img_backbone"].pop("init_cfg")  # the fork points at a checkpoint on its author's disk
+        cfg["view_transform"]["image_size"] = [384, 704]
+        cfg["view_transform"]["feature_size"] = [48, 88]
+    return cfg
+
+
+# the model dicts this package builds by name: MODELS.build(model_config("custom_data"))
+CONFIGS = dict(nuscenes=nuscenes_config, custom_data=custom_data_config)
+
+
+def model_config(name, **kwargs):
+    if name not in CONFIGS:
+        raise KeyError("unknown model config %r (known: %s)" % (name, ", ".join(sorted(CONFIGS))))
+    return CONFIGS[name](**kwargs)
+
+
 def surrogate_loss(outs, depth_loss=0.0):
     """A ground-truth-free scalar over every head output (a Gaussian-focal style term on the dense heat-map plus L1 terms on
     every regression head), so that backward reaches every parameter the real loss reaches.  Used only by the smoke-sized

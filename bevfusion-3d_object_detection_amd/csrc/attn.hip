@@ -11,6 +11,11 @@
 //   attn_bwd_kernel     per (b, h, key chunk): dS^T and A^T tiles in the accumulator layout feed dQ (reduction over keys)
 //                       directly; for dK, dV (reductions over queries) the two 16 x 16 tiles go through 1 KB of wave-private
 //                       LDS to swap their axes; dK, dV are final per key, dQ partial per chunk -> attn_out_combine
+// More than 256 queries (up to kMaxQ = 512, the fork's custom_data head has 500): the forward kernels take a query-block
+// grid axis (256 queries per block, the last one ragged; partial / opart are indexed by the global query, the combines do
+// not change); the backward stays ONE workgroup per (b, h, key chunk) that walks all query tiles for each key tile
+// (attn_bwd_kernel<DROP, 32>: 128 dQ accumulator registers, Q and dO of all 512 queries in LDS), so dK and dV are still
+// summed over all queries inside one wave in a fixed order and written final -- no cross-block reduction, no workspace.
 // Tensors are [B, L, E] row-major with E = H * 16 (head h = channels 16h .. 16h+15), bf16; softmax statistics fp32.
 // Dropout uses a counter hash of (seed, element index): the same mask is regenerated in the backward.
 #include "common.h"
@@ -23,7 +28,9 @@ typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kD = 16;        // head dim
-constexpr int kMaxQT = 16;    // up to 256 queries
+constexpr int kMaxQT = 16;    // query tiles per forward workgroup / narrow backward: 256 queries
+constexpr int kWideQT = 32;   // query tiles of the wide backward
+constexpr int kMaxQ = kWideQT * 16;  // 512 queries
 constexpr int kChunk = 512;   // keys per workgroup (4 waves x 8 key tiles)
 
 __device__ __forceinline__ float bf2f(bf16_t v) { return __uint_as_float((unsigned)v << 16); }
@@ -68,14 +75,15 @@ __global__ __launch_bounds__(256) void attn_lse_kernel(const bf16_t *__restrict_
   __shared__ float2 red[4][kMaxQT * 16];
   const int c = blockIdx.x, bh = blockIdx.y, b = bh / dm.H, h = bh - b * dm.H;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, ln = lane & 15, lg = lane >> 4;
-  const int NQ = (dm.Lq + 15) >> 4;
-  const bf16_t *Qb = Q + (size_t)b * dm.Lq * dm.E + h * kD, *Kb = K + (size_t)b * dm.Lk * dm.E + h * kD;
+  const int q0 = blockIdx.z * (kMaxQT * 16), Lq = min(dm.Lq - q0, kMaxQT * 16);  // this block's queries: q0 .. q0 + Lq - 1
+  const int NQ = (Lq + 15) >> 4;
+  const bf16_t *Qb = Q + ((size_t)b * dm.Lq + q0) * dm.E + h * kD, *Kb = K + (size_t)b * dm.Lk * dm.E + h * kD;
   float m[kMaxQT], l[kMaxQT];
   for (int t = 0; t < kMaxQT; ++t) { m[t] = -INFINITY; l[t] = 0.f; }
   // the workgroup keeps ALL queries: their MFMA operands stay in registers for the whole key loop (2 VGPRs per 16-query tile)
   s16x4 qreg[kMaxQT];
 #pragma unroll
-  for (int t = 0; t < kMaxQT; ++t) qreg[t] = (t < NQ && t * 16 + ln < dm.Lq) ? ld4(Qb + (size_t)(t * 16 + ln) * dm.E + lg * 4) : zero4();
+  for (int t = 0; t < kMaxQT; ++t) qreg[t] = (t < NQ && t * 16 + ln < Lq) ? ld4(Qb + (size_t)(t * 16 + ln) * dm.E + lg * 4) : zero4();
   const int key0 = c * kChunk + wave * (kChunk / 4);
   for (int kt = 0; kt < kChunk / 64; ++kt) {
     const int key = key0 + kt * 16 + ln;       // A operand row (key) of this lane
@@ -113,7 +121,7 @@ __global__ __launch_bounds__(256) void attn_lse_kernel(const bf16_t *__restrict_
     if (lg == 0) red[wave][t * 16 + ln] = make_float2(mm, ll);
   }
   __syncthreads();
-  for (int q = threadIdx.x; q < dm.Lq; q += 256) {
+  for (int q = threadIdx.x; q < Lq; q += 256) {
     float mm = -INFINITY, ll = 0.f;
     for (int w = 0; w < 4; ++w) {
       float2 v = red[w][q];
@@ -121,7 +129,7 @@ __global__ __launch_bounds__(256) void attn_lse_kernel(const bf16_t *__restrict_
       ll = (M == -INFINITY) ? 0.f : ll * __expf(mm - M) + v.y * __expf(v.x - M);
       mm = M;
     }
-    partial[((size_t)bh * dm.nchunk + c) * dm.Lq + q] = make_float2(mm, ll);
+    partial[((size_t)bh * dm.nchunk + c) * dm.Lq + q0 + q] = make_float2(mm, ll);
   }
 }
 
@@ -149,18 +157,19 @@ __global__ __launch_bounds__(256) void attn_out_kernel(const bf16_t *__restrict_
   __shared__ float osum[kMaxQT * 16 * kD];      // cross-wave reduction of O
   const int c = blockIdx.x, bh = blockIdx.y, b = bh / dm.H, h = bh - b * dm.H;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, ln = lane & 15, lg = lane >> 4;
-  const int NQ = (dm.Lq + 15) >> 4;
-  const bf16_t *Qb = Q + (size_t)b * dm.Lq * dm.E + h * kD, *Kb = K + (size_t)b * dm.Lk * dm.E + h * kD,
+  const int q0 = blockIdx.z * (kMaxQT * 16), Lq = min(dm.Lq - q0, kMaxQT * 16);  // this block's queries: q0 .. q0 + Lq - 1
+  const int NQ = (Lq + 15) >> 4;
+  const bf16_t *Qb = Q + ((size_t)b * dm.Lq + q0) * dm.E + h * kD, *Kb = K + (size_t)b * dm.Lk * dm.E + h * kD,
                *Vb = V + (size_t)b * dm.Lk * dm.E + h * kD;
-  const float *lb = lse + (size_t)bh * dm.Lq;
+  const float *lb = lse + (size_t)bh * dm.Lq + q0;
   for (int i = threadIdx.x; i < NQ * 16 * kD; i += 256) osum[i] = 0.f;
   f32x4 o[kMaxQT];
   for (int t = 0; t < kMaxQT; ++t) o[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
   float lq_[kMaxQT];
-  for (int t = 0; t < kMaxQT; ++t) lq_[t] = (t < NQ && t * 16 + ln < dm.Lq) ? lb[t * 16 + ln] : 0.f;
-  s16x4 qreg[kMaxQT];  // all query tiles in registers for the whole key loop
+  for (int t = 0; t < kMaxQT; ++t) lq_[t] = (t < NQ && t * 16 + ln < Lq) ? lb[t * 16 + ln] : 0.f;
+  s16x4 qreg[kMaxQT];  // all query tiles of the block in registers for the whole key loop
 #pragma unroll
-  for (int t = 0; t < kMaxQT; ++t) qreg[t] = (t < NQ && t * 16 + ln < dm.Lq) ? ld4(Qb + (size_t)(t * 16 + ln) * dm.E + lg * 4) : zero4();
+  for (int t = 0; t < kMaxQT; ++t) qreg[t] = (t < NQ && t * 16 + ln < Lq) ? ld4(Qb + (size_t)(t * 16 + ln) * dm.E + lg * 4) : zero4();
   const unsigned long long seed = eff_seed(dm);
   const int key0 = c * kChunk + wave * (kChunk / 4);
   for (int kt = 0; kt < kChunk / 64; ++kt) {
@@ -187,8 +196,8 @@ __global__ __launch_bounds__(256) void attn_out_kernel(const bf16_t *__restrict_
       s16x4 pa;                                                  // A operand of P V: A[m = q = ln][k = keys lg*4 + i]
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        float p = (kbase + i < dm.Lk && q < dm.Lq) ? __expf(s[i] * dm.scale - lq_[t]) : 0.f;
-        if (DROP) p = keep(seed, ((unsigned)bh * dm.Lq + q) * dm.Lk, kbase + i, dm.thresh24) ? p * dm.inv_keep : 0.f;
+        float p = (kbase + i < dm.Lk && q < Lq) ? __expf(s[i] * dm.scale - lq_[t]) : 0.f;
+        if (DROP) p = keep(seed, ((unsigned)bh * dm.Lq + q0 + q) * dm.Lk, kbase + i, dm.thresh24) ? p * dm.inv_keep : 0.f;
         pa[i] = (short)f2bf(p);
       }
       o[t] = MFMA16(pa, vb, o[t]);  // O[q = t*16 + lg*4 + i][dv = ln]
@@ -207,8 +216,8 @@ __global__ __launch_bounds__(256) void attn_out_kernel(const bf16_t *__restrict_
     }
     __syncthreads();
   }
-  float *dst = opart + ((size_t)bh * dm.nchunk + c) * dm.Lq * kD;
-  for (int i = threadIdx.x; i < dm.Lq * kD; i += 256) dst[i] = osum[i];
+  float *dst = opart + (((size_t)bh * dm.nchunk + c) * dm.Lq + q0) * kD;
+  for (int i = threadIdx.x; i < Lq * kD; i += 256) dst[i] = osum[i];
 }
 
 // O[b][q][h*16 + dv] = sum_c opart (bf16 out)
@@ -227,18 +236,25 @@ __global__ __launch_bounds__(256) void attn_out_combine(const float *__restrict_
 }
 
 // ---------------------------------------------------------------------------------------------------- backward
-// dqpart[((bh * nchunk + c) * Lq + q) * 16 + d]; dK, dV final.
-template <bool DROP>
+// dqpart[((bh * nchunk + c) * Lq + q) * 16 + d]; dK, dV final.  NQT = query tiles the workgroup walks per key tile (compile-time:
+// dq[] must keep constant indices to stay in registers): kMaxQT for Lq <= 256, kWideQT above.  The wide instantiation holds
+// Q and dO of 512 queries in LDS (36 KB) and reuses that space for the cross-wave dQ reduction after the key loop (32 KB), so
+// it stays inside the 64 KB a kernel gets without the dynamic-size attribute (47 KB in all).
+template <bool DROP, int NQT>
 __global__ __launch_bounds__(256) void attn_bwd_kernel(const bf16_t *__restrict__ Q, const bf16_t *__restrict__ K,
                                                        const bf16_t *__restrict__ V, const bf16_t *__restrict__ O,
                                                        const bf16_t *__restrict__ dO, const float *__restrict__ lse,
                                                        Dims dm, float *__restrict__ dqpart, bf16_t *__restrict__ dK,
                                                        bf16_t *__restrict__ dV) {
-  __shared__ bf16_t qs[kMaxQT * 16][kD + 2], dos[kMaxQT * 16][kD + 2];  // Q, dO of this (b, h): transposed reads
-  __shared__ float dsum[kMaxQT * 16], ls[kMaxQT * 16];                   // D_q = rowsum(dO o O), lse
+  constexpr bool kAlias = NQT > kMaxQT;
+  __shared__ __attribute__((aligned(16))) bf16_t qd[2 * NQT * 16][kD + 2];  // Q, dO of this (b, h): transposed reads
+  bf16_t (*qs)[kD + 2] = qd, (*dos)[kD + 2] = qd + NQT * 16;
+  static_assert(sizeof(qd) >= NQT * 16 * kD * sizeof(float) || !kAlias, "the dQ reduction must fit in the Q / dO staging space");
+  __shared__ float dsum[NQT * 16], ls[NQT * 16];                         // D_q = rowsum(dO o O), lse
   __shared__ bf16_t kts[4][16][kD + 2];                                  // per wave: current K tile (transposed reads)
   __shared__ __attribute__((aligned(8))) bf16_t tds[4][16][16], tas[4][16][16];  // per wave: dS and A tiles, [key][query]
-  __shared__ float dqs[kMaxQT * 16 * kD];
+  __shared__ float dqs_own[kAlias ? 1 : NQT * 16 * kD];
+  float *dqs = kAlias ? (float *)&qd[0][0] : dqs_own;
   const int c = blockIdx.x, bh = blockIdx.y, b = bh / dm.H, h = bh - b * dm.H;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, ln = lane & 15, lg = lane >> 4;
   const int NQ = (dm.Lq + 15) >> 4;
@@ -255,10 +271,11 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const bf16_t *__restrict_
     dsum[i] = acc;
     ls[i] = i < dm.Lq ? lse[(size_t)bh * dm.Lq + i] : 0.f;
   }
-  for (int i = threadIdx.x; i < NQ * 16 * kD; i += 256) dqs[i] = 0.f;
+  if (!kAlias)
+    for (int i = threadIdx.x; i < NQ * 16 * kD; i += 256) dqs[i] = 0.f;
   __syncthreads();
-  f32x4 dq[kMaxQT];
-  for (int t = 0; t < kMaxQT; ++t) dq[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  f32x4 dq[NQT];
+  for (int t = 0; t < NQT; ++t) dq[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
   const unsigned long long seed = eff_seed(dm);
   const int key0 = c * kChunk + wave * (kChunk / 4);
   for (int kt = 0; kt < kChunk / 64; ++kt) {
@@ -276,7 +293,7 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const bf16_t *__restrict_
     const int kbase = key0 + kt * 16 + lg * 4;
     f32x4 dk = {0.f, 0.f, 0.f, 0.f}, dv = {0.f, 0.f, 0.f, 0.f};  // [key = lg*4 + i][d = ln]
 #pragma unroll
-    for (int t = 0; t < kMaxQT; ++t) {
+    for (int t = 0; t < NQT; ++t) {
       if (t >= NQ) continue;
       const int q = t * 16 + ln;  // this lane's query as an MFMA row / column index
       s16x4 qr, gr;               // Q[q][4lg..], dO[q][4lg..] (row-major vectors)
@@ -326,10 +343,15 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const bf16_t *__restrict_
     }
     __builtin_amdgcn_wave_barrier();
   }
+  if (kAlias) {  // every wave is done with Q / dO: their space becomes the dQ reduction buffer
+    __syncthreads();
+    for (int i = threadIdx.x; i < NQ * 16 * kD; i += 256) dqs[i] = 0.f;
+    __syncthreads();
+  }
   for (int w = 0; w < 4; ++w) {
     if (wave == w) {
 #pragma unroll
-      for (int t = 0; t < kMaxQT; ++t) {
+      for (int t = 0; t < NQT; ++t) {
         if (t >= NQ) continue;
 #pragma unroll
         for (int i = 0; i < 4; ++i) dqs[(t * 16 + lg * 4 + i) * kD + ln] += dq[t][i];
@@ -354,7 +376,7 @@ __global__ __launch_bounds__(256) void attn_mask_kernel(Dims dm, unsigned char *
 
 inline int make_dims(int B, int H, int Lq, int Lk, float scale, float dropout_p, unsigned long long seed,
                      const unsigned long long *seed_dev, Dims &dm) {
-  if (B <= 0 || H <= 0 || Lq <= 0 || Lq > kMaxQT * 16 || Lk <= 0 || !(dropout_p >= 0.f && dropout_p < 1.f)) return -1;
+  if (B <= 0 || H <= 0 || Lq <= 0 || Lq > kMaxQ || Lk <= 0 || !(dropout_p >= 0.f && dropout_p < 1.f)) return -1;
   dm.B = B; dm.H = H; dm.Lq = Lq; dm.Lk = Lk; dm.E = H * kD;
   dm.nchunk = (Lk + kChunk - 1) / kChunk;
   dm.scale = scale;
@@ -370,6 +392,8 @@ inline int make_dims(int B, int H, int Lq, int Lk, float scale, float dropout_p,
 
 using namespace bfhip;
 
+BFHIP_EXPORT int bfhip_attn_max_queries(void) { return kMaxQ; }
+
 BFHIP_EXPORT size_t bfhip_attn_workspace_bytes(int B, int H, int Lq, int Lk) {
   if (B <= 0 || H <= 0 || Lq <= 0 || Lk <= 0) return 0;
   size_t nchunk = (Lk + kChunk - 1) / kChunk;
@@ -383,13 +407,13 @@ BFHIP_EXPORT int bfhip_attn_fwd(const void *Q, const void *K, const void *V, int
                                 size_t workspace_bytes, void *stream_) {
   hipStream_t s = (hipStream_t)stream_;
   Dims dm;
-  BFHIP_REQUIRE(make_dims(B, H, Lq, Lk, scale, dropout_p, seed, seed_dev, dm) == 0, "attn_fwd: unsupported sizes B=%d H=%d Lq=%d Lk=%d (Lq <= 256, head dim 16)", B, H, Lq, Lk);
+  BFHIP_REQUIRE(make_dims(B, H, Lq, Lk, scale, dropout_p, seed, seed_dev, dm) == 0, "attn_fwd: unsupported sizes B=%d H=%d Lq=%d Lk=%d (Lq <= 512, head dim 16)", B, H, Lq, Lk);
   BFHIP_REQUIRE(Q && K && V && O && lse, "attn_fwd: null pointer");
   BFHIP_REQUIRE(((uintptr_t)Q % 8) == 0 && ((uintptr_t)K % 8) == 0 && ((uintptr_t)V % 8) == 0, "attn_fwd: tensors must be 8-byte aligned");
   if (!workspace || workspace_bytes < bfhip_attn_workspace_bytes(B, H, Lq, Lk)) { set_error("attn_fwd: workspace too small"); return BFHIP_E_WORKSPACE; }
   float2 *lpart = (float2 *)workspace;
   float *opart = (float *)((char *)workspace + align_up((size_t)B * H * dm.nchunk * Lq * sizeof(float2), 256));
-  dim3 grid(dm.nchunk, B * H);
+  dim3 grid(dm.nchunk, B * H, ceil_div(Lq, kMaxQT * 16));  // z: blocks of 256 queries
   hipLaunchKernelGGL(attn_lse_kernel, grid, dim3(256), 0, s, (const bf16_t *)Q, (const bf16_t *)K, dm, lpart);
   hipLaunchKernelGGL(attn_lse_combine, dim3(ceil_div((long long)B * H * Lq, 256)), dim3(256), 0, s, lpart, dm, lse);
   if (dropout_p > 0.f)
@@ -411,10 +435,15 @@ BFHIP_EXPORT int bfhip_attn_bwd(const void *Q, const void *K, const void *V, con
   if (!workspace || workspace_bytes < bfhip_attn_workspace_bytes(B, H, Lq, Lk)) { set_error("attn_bwd: workspace too small"); return BFHIP_E_WORKSPACE; }
   float *dqpart = (float *)((char *)workspace + align_up((size_t)B * H * dm.nchunk * Lq * sizeof(float2), 256));
   dim3 grid(dm.nchunk, B * H);
-  if (dropout_p > 0.f)
-    hipLaunchKernelGGL(attn_bwd_kernel<true>, grid, dim3(256), 0, s, (const bf16_t *)Q, (const bf16_t *)K, (const bf16_t *)V, (const bf16_t *)O, (const bf16_t *)dO, lse, dm, dqpart, (bf16_t *)dK, (bf16_t *)dV);
-  else
-    hipLaunchKernelGGL(attn_bwd_kernel<false>, grid, dim3(256), 0, s, (const bf16_t *)Q, (const bf16_t *)K, (const bf16_t *)V, (const bf16_t *)O, (const bf16_t *)dO, lse, dm, dqpart, (bf16_t *)dK, (bf16_t *)dV);
+#define BFHIP_ATTN_BWD(DROP, NQT)                                                                                         \
+  hipLaunchKernelGGL((attn_bwd_kernel<DROP, NQT>), grid, dim3(256), 0, s, (const bf16_t *)Q, (const bf16_t *)K,            \
+                     (const bf16_t *)V, (const bf16_t *)O, (const bf16_t *)dO, lse, dm, dqpart, (bf16_t *)dK, (bf16_t *)dV)
+  if (Lq <= kMaxQT * 16) {
+    if (dropout_p > 0.f) BFHIP_ATTN_BWD(true, kMaxQT); else BFHIP_ATTN_BWD(false, kMaxQT);
+  } else {
+    if (dropout_p > 0.f) BFHIP_ATTN_BWD(true, kWideQT); else BFHIP_ATTN_BWD(false, kWideQT);
+  }
+#undef BFHIP_ATTN_BWD
   hipLaunchKernelGGL(attn_out_combine, dim3(ceil_div((long long)B * H * Lq * kD, 256)), dim3(256), 0, s, dqpart, dm, (bf16_t *)dQ);
   return check_launch("attn_bwd");
 }

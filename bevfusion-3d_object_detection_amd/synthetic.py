@@ -32,6 +32,12 @@ NUSC = dict(
     C=80,
 )
 
+# the reference's custom_data configs (projects/BEVFusion/configs/custom_data/lidar-cam_custom.py:7,47-57, lidar_custom.py:17-23):
+# what differs from NUSC; camera_rig(**CUSTOM["rig"]) and gt_boxes(classes=CUSTOM["classes"]) give inputs of these shapes
+CUSTOM = dict(NUSC, image_size=(384, 704), feature_size=(48, 88), num_cams=5, point_features=3, num_proposals=500,
+              classes=(0, 1, 3, 7, 8),  # car, truck, bus, bicycle, pedestrian: rows of _CLASS_SIZES
+              rig=dict(num_cams=5, resize=0.48, crop=(32, 48)))
+
 # HDL-32E: 32 beams from -30.67 to +10.67 degrees
 _ELEV = np.deg2rad(np.linspace(-30.67, 10.67, 32))
 
@@ -111,12 +117,18 @@ def _cam2lidar(yaw_deg, forward=0.0, lateral=0.0, z=-0.3, pitch_deg=0.0, roll_de
     return T
 
 
-def camera_rig(batch=1, seed=None, train_aug=False):
-    """Returns dict of f32 arrays: camera_intrinsics [B,6,4,4], camera2lidar [B,6,4,4],
-    lidar2image [B,6,4,4], img_aug_matrix [B,6,4,4], lidar_aug_matrix [B,4,4].
+def camera_rig(batch=1, seed=None, train_aug=False, num_cams=6, resize=0.48, crop=(32, 176)):
+    """Returns dict of f32 arrays: camera_intrinsics [B,N,4,4], camera2lidar [B,N,4,4],
+    lidar2image [B,N,4,4], img_aug_matrix [B,N,4,4], lidar_aug_matrix [B,4,4] with N = num_cams: the first num_cams
+    cameras of the nominal rig.  img_aug_matrix = `resize`, then a crop at (x, y) = `crop`.
+
+    The reference's custom_data configs (five cameras, 384x704 images, test resize 0.48) come without their dataset, so
+    there is no calibration to imitate: CUSTOM below keeps the nominal 1600x900 source, for which resize 0.48 gives 768x432
+    and the 704x384 window is cropped at (32, 48).
 
     train_aug: seeded rotation in +-pi/4, scale in [0.9,1.1], translation sigma 0.5 for the lidar
     augmentation (reference config ...lidar-cam...py:92-96); image aug stays the eval one."""
+    assert 1 <= num_cams <= 6, num_cams
     yaws = [0.0, -55.0, 55.0, 180.0, 110.0, -110.0]  # F, FR, FL, B, BL, BR
     fwd = [1.70, 1.55, 1.55, 0.05, 1.05, 1.05]
     lat = [0.0, 0.50, -0.50, 0.0, -0.48, 0.48]
@@ -124,9 +136,9 @@ def camera_rig(batch=1, seed=None, train_aug=False):
     # real sample quoted in SURVEY.md 8 (kept ~1.83 M, ~97 k intervals, mean length ~19, max ~890)
     pitch = [0.92, -0.69, 1.15, -1.04, 0.58, -1.27]
     roll = [-0.35, 1.04, 0.58, -0.81, 1.27, 0.46]
-    K = np.zeros((6, 4, 4))
-    c2l = np.zeros((6, 4, 4))
-    for i in range(6):
+    K = np.zeros((num_cams, 4, 4))
+    c2l = np.zeros((num_cams, 4, 4))
+    for i in range(num_cams):
         fx = 809.22 if i == 3 else 1266.42
         cx, cy = (829.22, 481.78) if i == 3 else (816.27, 491.51)
         K[i] = np.eye(4)
@@ -136,13 +148,13 @@ def camera_rig(batch=1, seed=None, train_aug=False):
     l2c = np.linalg.inv(c2l)
     l2i = K @ l2c
     aug = np.eye(4)
-    aug[0, 0] = aug[1, 1] = 0.48
-    aug[0, 3], aug[1, 3] = -32.0, -176.0
+    aug[0, 0] = aug[1, 1] = resize
+    aug[0, 3], aug[1, 3] = -float(crop[0]), -float(crop[1])
     out = dict(
-        camera_intrinsics=np.broadcast_to(K, (batch, 6, 4, 4)).astype(np.float32).copy(),
-        camera2lidar=np.broadcast_to(c2l, (batch, 6, 4, 4)).astype(np.float32).copy(),
-        lidar2image=np.broadcast_to(l2i, (batch, 6, 4, 4)).astype(np.float32).copy(),
-        img_aug_matrix=np.broadcast_to(aug, (batch, 6, 4, 4)).astype(np.float32).copy(),
+        camera_intrinsics=np.broadcast_to(K, (batch, num_cams, 4, 4)).astype(np.float32).copy(),
+        camera2lidar=np.broadcast_to(c2l, (batch, num_cams, 4, 4)).astype(np.float32).copy(),
+        lidar2image=np.broadcast_to(l2i, (batch, num_cams, 4, 4)).astype(np.float32).copy(),
+        img_aug_matrix=np.broadcast_to(aug, (batch, num_cams, 4, 4)).astype(np.float32).copy(),
     )
     la = np.broadcast_to(np.eye(4), (batch, 4, 4)).copy()
     if train_aug:
@@ -196,16 +208,24 @@ _CLASS_SIZES = np.array([
 _CLASS_FREQ = np.array([0.43, 0.08, 0.013, 0.014, 0.022, 0.13, 0.011, 0.01, 0.20, 0.09])
 
 
-def gt_boxes(seed=3000, n=None, point_cloud_range=NUSC["point_cloud_range"]):
+def gt_boxes(seed=3000, n=None, point_cloud_range=NUSC["point_cloud_range"], classes=None):
     """Synthetic ground truth of one frame: boxes f32[G, 9] = (x, y, z_bottom, dx, dy, dz, yaw, vx, vy) in the LiDAR
     frame (the layout of `LiDARInstance3DBoxes.tensor` with velocities) and labels i64[G].  G ~ U(15, 60) unless given;
-    class frequencies and sizes are nuScenes-like, centres stay inside the detection range."""
+    class frequencies and sizes are nuScenes-like, centres stay inside the detection range.  classes: rows of
+    _CLASS_SIZES to draw from (their relative frequencies kept), relabelled 0 .. len(classes) - 1."""
     rs = np.random.RandomState(seed)
     g = int(rs.randint(15, 61)) if n is None else int(n)
-    labels = rs.choice(10, size=g, p=_CLASS_FREQ / _CLASS_FREQ.sum()).astype(np.int64)
+    if classes is None:
+        labels = rs.choice(10, size=g, p=_CLASS_FREQ / _CLASS_FREQ.sum()).astype(np.int64)
+        rows = labels
+    else:
+        classes = np.asarray(classes, np.int64)
+        freq = _CLASS_FREQ[classes]
+        labels = rs.choice(len(classes), size=g, p=freq / freq.sum()).astype(np.int64)
+        rows = classes[labels]
     lo, hi = np.array(point_cloud_range[:2], np.float32) + 1.0, np.array(point_cloud_range[3:5], np.float32) - 1.0
     xy = (rs.uniform(0, 1, (g, 2)) * (hi - lo) + lo).astype(np.float32)
-    size = _CLASS_SIZES[labels] * rs.uniform(0.85, 1.2, (g, 3)).astype(np.float32)
+    size = _CLASS_SIZES[rows] * rs.uniform(0.85, 1.2, (g, 3)).astype(np.float32)
     z = rs.uniform(-2.2, -1.2, (g, 1)).astype(np.float32)
     yaw = rs.uniform(-np.pi, np.pi, (g, 1)).astype(np.float32)
     vel = (rs.normal(0, 2.0, (g, 2)) * (rs.uniform(0, 1, (g, 1)) < 0.4)).astype(np.float32)

@@ -382,11 +382,14 @@ int bfhip_xty(const void *X, const void *Y, long long K, int M, int N, int dtype
  * Cross attention of few queries over very many keys (the TransFusion decoder layer: 200 queries x 32 400 BEV cells,
  *   8 heads of 16 channels, dropout on the attention weights; BF/transformer.py:60-105, mmcv MultiheadAttention ->
  *   torch scaled_dot_product_attention).  Q [B, Lq, H*16], K / V [B, Lk, H*16], O, dO, dQ, dK, dV alike: bf16, row-major;
- *   head h = channels 16h..16h+15; Lq <= 256.  lse f32[B*H, Lq] (log-sum-exp of the scaled scores) links fwd and bwd.
+ *   head h = channels 16h..16h+15; Lq <= bfhip_attn_max_queries() = 512 (host-only; up to 256 queries one workgroup per
+ *   key chunk keeps them all, above that the forward adds a query-block grid axis and the backward walks 32 query tiles per
+ *   key tile: dK / dV are still final per key, no extra workspace).  lse f32[B*H, Lq] (log-sum-exp of the scaled scores) links fwd and bwd.
  *   The key axis is split over the chip; combines run in a fixed order (bit-reproducible).  dropout_p in [0, 1): keep
  *   mask = counter hash of (seed, b, h, query, key), regenerated in the backward; bfhip_attn_dropout_mask writes it
  *   out (u8[B*H, Lq, Lk]) for tests.  The workspace is shared by fwd and bwd.
  * --------------------------------------------------------------------------------------- */
+int bfhip_attn_max_queries(void);
 size_t bfhip_attn_workspace_bytes(int B, int H, int Lq, int Lk);
 int bfhip_attn_fwd(const void *Q, const void *K, const void *V, int B, int H, int Lq, int Lk, float scale,
                    float dropout_p, unsigned long long seed, const unsigned long long *seed_dev, void *O, float *lse,
