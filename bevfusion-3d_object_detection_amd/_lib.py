@@ -134,6 +134,12 @@ SIGNATURES = {
     "bfhip_swin_attn_fwd": (_c_int, [_c_vp, ctypes.c_longlong, _c_vp] + [_c_int] * 5 + [ctypes.c_float, _c_vp, _c_vp, _c_vp]),
     "bfhip_swin_attn_bwd": (_c_int, [_c_vp, ctypes.c_longlong, _c_vp, _c_vp, _c_vp, _c_vp] + [_c_int] * 5 +
                             [ctypes.c_float, _c_vp, _c_vp, _c_int, _c_vp]),
+    "bfhip_layernorm_supported": (_c_int, [ctypes.c_longlong, _c_int, _c_int, _c_int]),
+    "bfhip_layernorm_parts": (_c_int, [ctypes.c_longlong, _c_int]),
+    "bfhip_layernorm_fwd": (_c_int, [_c_vp, _c_vp, _c_vp, ctypes.c_longlong, _c_vp, _c_vp, ctypes.c_longlong, _c_int, ctypes.c_float] +
+                            [_c_int] * 3 + [_c_vp] * 4),
+    "bfhip_layernorm_bwd": (_c_int, [_c_vp] * 6 + [ctypes.c_longlong, ctypes.c_longlong] + [_c_int] * 4 + [_c_vp] * 3 + [_c_int] +
+                            [_c_vp] * 3),
 }
 
 _lib = None

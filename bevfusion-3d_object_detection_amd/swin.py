@@ -11,6 +11,13 @@ Activations are [B, H, W, C] throughout (what the Linears and LayerNorms want); 
 Attention runs in csrc/swin_attn.hip when it can: the qkv Linear's output goes into the kernel as it is, and the cyclic
 shift, window partition, bias, mask and softmax happen there.  Everything else (CPU, fp32, attention dropout in training,
 other window or head sizes, BFHIP_SWIN_ATTN=0) takes the plain-torch path of the published algorithm.
+
+With BFHIP_SWIN_LN=1 (layernorm.ENABLED; it ships off) the token-wise glue runs in csrc/layernorm.hip
+(layernorm.py) on the GPU: a block is LayerNorm, then residual add + drop path +
+LayerNorm in one launch, then residual add + drop path, three launches over the fp32 stream instead of eight library kernels;
+the patch-embedding, patch-merging and output norms use the same kernel.  The switch off, the CPU, or an
+autocast dtype other than bf16 keep the nn.LayerNorm modules and torch adds.  Module tree, parameters and state-dict keys are
+the same either way.
 """
 import os
 
@@ -19,7 +26,7 @@ import torch.nn.functional as F
 from torch import nn
 from torch.utils.checkpoint import checkpoint
 
-from . import _lib
+from . import _lib, layernorm
 from .linear_rows import linear_rows
 from .registry import MODELS
 
@@ -124,6 +131,36 @@ def drop_path(x, p, training):
     return x * (mask / keep)
 
 
+def drop_path_scale(x, p, training):
+    """The per-sample factor drop_path(x, p, training) multiplies by, as f32 [B], or None where drop_path is the identity.  The
+    mask is drawn by the same call with the same shape and dtype, so a seeded run drops the same samples either way."""
+    if p == 0.0 or not training:
+        return None
+    keep = 1.0 - p
+    mask = x.new_empty((x.shape[0],) + (1,) * (x.dim() - 1)).bernoulli_(keep)
+    return (mask / keep).reshape(-1).float()
+
+
+def _ln_kernel_path(x):
+    """Do the LayerNorms and residual adds around x go through layernorm.py?  (It still falls back per call for what the kernels
+    do not cover.)  Off: exactly the module calls and torch arithmetic of the plain path."""
+    if not (layernorm.ENABLED and x.is_cuda):
+        return False
+    return not torch.is_autocast_enabled("cuda") or torch.get_autocast_dtype("cuda") == torch.bfloat16
+
+
+def _norm(ln, x, to_linear=False):
+    """nn.LayerNorm `ln` over x [..., C].  On the kernel path the output has the dtype its consumer sees today: fp32 under
+    autocast (x's dtype without), or, where the consumer is a Linear (`to_linear`), the bf16 that autocast casts it to."""
+    if not (_ln_kernel_path(x) and ln.elementwise_affine and ln.bias is not None and len(ln.normalized_shape) == 1):
+        return ln(x)
+    if torch.is_autocast_enabled("cuda"):
+        out = torch.bfloat16 if to_linear else torch.float32
+    else:
+        out = x.dtype
+    return layernorm.layer_norm_rows(x, ln.weight, ln.bias, ln.eps, out)
+
+
 def _rows(lin, x):
     """nn.Linear over the last axis of [.., C] through linear_rows ([tokens, C] matrix: split-K weight gradient)."""
     return linear_rows(x.reshape(-1, x.shape[-1]), lin.weight, lin.bias).view(*x.shape[:-1], lin.out_features)
@@ -193,8 +230,11 @@ class ShiftWindowMSA(nn.Module):
 
     def forward(self, x):
         """x [B, H, W, C] (the LayerNorm's output) -> attention output [B, H, W, C], drop path applied."""
-        y = self._forward_hip(x) if self.hip_eligible(x) else self._forward_torch(x)
-        return drop_path(y, self.drop_path_rate, self.training)
+        return drop_path(self.branch(x), self.drop_path_rate, self.training)
+
+    def branch(self, x):
+        """forward() before its drop path (SwinBlock hands the drop-path factor to the residual kernel instead)."""
+        return self._forward_hip(x) if self.hip_eligible(x) else self._forward_torch(x)
 
     def _forward_hip(self, x):
         B, H, W, C = x.shape
@@ -266,8 +306,17 @@ class SwinBlock(nn.Module):
         self.ffn = SwinFFN(embed_dims, feedforward_channels, drop_rate)
 
     def _inner(self, x):
-        x = x + self.attn(self.norm1(x))
-        return x + drop_path(self.ffn(self.norm2(x)), self.drop_path_rate, self.training)
+        n1, n2 = self.norm1, self.norm2
+        if not (_ln_kernel_path(x) and n1.elementwise_affine and n2.elementwise_affine and n1.bias is not None and n2.bias is not None):
+            x = x + self.attn(self.norm1(x))
+            return x + drop_path(self.ffn(self.norm2(x)), self.drop_path_rate, self.training)
+        # three launches of csrc/layernorm.hip; the masks are drawn where drop_path drew them (after each branch is computed)
+        ydt = torch.bfloat16 if torch.is_autocast_enabled("cuda") else x.dtype  # what the qkv / fc1 Linear sees today
+        a = self.attn.branch(layernorm.layer_norm_rows(x, n1.weight, n1.bias, n1.eps, ydt))
+        x, y = layernorm.add_layer_norm_rows(x, a, drop_path_scale(a, self.drop_path_rate, self.training), n2.weight, n2.bias,
+                                             n2.eps, ydt)
+        f = self.ffn(y)
+        return layernorm.scaled_add_rows(x, f, drop_path_scale(f, self.drop_path_rate, self.training))
 
     def forward(self, x):
         if self.with_cp and x.requires_grad:
@@ -292,7 +341,7 @@ class PatchMerging(nn.Module):
         return x.view(B, H // 2, 2, W // 2, 2, C).permute(0, 1, 3, 5, 2, 4).reshape(B, H // 2, W // 2, 4 * C)
 
     def forward(self, x):
-        return _rows(self.reduction, self.norm(self.gather(x)))
+        return _rows(self.reduction, _norm(self.norm, self.gather(x), to_linear=True))
 
 
 class SwinBlockSequence(nn.Module):
@@ -325,12 +374,17 @@ class PatchEmbed(nn.Module):
         if x.is_cuda:
             x = x.contiguous(memory_format=torch.channels_last)  # the permute below is then the map's own memory order
         x = self.projection(x).permute(0, 2, 3, 1)
-        return self.norm(x) if self.norm is not None else x.contiguous()
+        return _norm(self.norm, x) if self.norm is not None else x.contiguous()
 
 
 class SwinTransformer(nn.Module):
     """mmdet.SwinTransformer with the arguments of the reference's config.  `init_cfg` and `convert_weights` are stored and
-    nothing is fetched; converting the keys of an original-format checkpoint is not done here."""
+    nothing is fetched; converting the keys of an original-format checkpoint is not done here.
+
+    `frozen_stages` follows mmdet 3.x's `_freeze_stages` from knowledge of that package (parity unpinned, like the rest of the
+    file): with frozen_stages >= 0 the patch embedding and `drop_after_pos` go to eval with requires_grad off; for i in
+    1 .. frozen_stages so do `stages[i - 1]` (its patch merging included) and `norm{i-1}` when that index is an output.  train()
+    re-applies it, so a frozen part stays in eval."""
 
     def __init__(self, pretrain_img_size=224, in_channels=3, embed_dims=96, patch_size=4, window_size=7, mlp_ratio=4,
                  depths=(2, 2, 6, 2), num_heads=(3, 6, 12, 24), strides=(4, 2, 2, 2), out_indices=(0, 1, 2, 3), qkv_bias=True,
@@ -340,7 +394,8 @@ class SwinTransformer(nn.Module):
         assert strides[0] == patch_size, "the patch embedding's stride is the patch size"
         assert not use_abs_pos_embed, "absolute position embedding is not built (no reference config uses it)"
         assert tuple(strides[1:]) == (2,) * (len(depths) - 1), "patch merging is 2 x 2"
-        assert frozen_stages == -1, "frozen stages are not built"
+        assert -1 <= frozen_stages <= len(depths), "frozen_stages counts stages"
+        self.frozen_stages = frozen_stages
         self.convert_weights, self.init_cfg, self.pretrained = convert_weights, init_cfg, pretrained
         self.out_indices = tuple(out_indices)
         self.patch_embed = PatchEmbed(in_channels, embed_dims, patch_size, strides[0], patch_norm)
@@ -360,6 +415,26 @@ class SwinTransformer(nn.Module):
         for i in self.out_indices:
             self.add_module("norm%d" % i, nn.LayerNorm(self.num_features[i]))
         self.apply(self._init)
+        self._freeze_stages()
+
+    def _freeze_stages(self):
+        def freeze(m):
+            m.eval()
+            for p in m.parameters():
+                p.requires_grad = False
+
+        if self.frozen_stages >= 0:
+            freeze(self.patch_embed)
+            self.drop_after_pos.eval()
+        for i in range(1, self.frozen_stages + 1):
+            if i - 1 in self.out_indices:
+                freeze(getattr(self, "norm%d" % (i - 1)))
+            freeze(self.stages[i - 1])
+
+    def train(self, mode=True):
+        super().train(mode)
+        self._freeze_stages()
+        return self
 
     @staticmethod
     def _init(m):
@@ -377,7 +452,7 @@ class SwinTransformer(nn.Module):
         for i, stage in enumerate(self.stages):
             x, out = stage(x)
             if i in self.out_indices:
-                outs.append(getattr(self, "norm%d" % i)(out).permute(0, 3, 1, 2))  # [B, C, H, W] view: channels-last
+                outs.append(_norm(getattr(self, "norm%d" % i), out).permute(0, 3, 1, 2))  # [B, C, H, W] view: channels-last
         return tuple(outs)
 
 

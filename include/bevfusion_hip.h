@@ -620,6 +620,35 @@ int bfhip_swin_attn_bwd(const void *qkv, long long qkv_pitch, const float *bias,
                         const float *lse, int B, int Hp, int Wp, int heads, int shift, float scale, void *dqkv,
                         float *dbias_partial, int parts, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Row-wise LayerNorm with the residual update in front of it (csrc/layernorm.hip): the token-wise glue of a transformer block
+ *   (mmdet's SwinBlock: LayerNorm, cast, drop path, residual add, twice per block) over a row-major [M, C] matrix.
+ *   dtypes 0 = f32, 1 = bf16: x_dtype for x / s / dsum / dx, branch_dtype for branch / dbranch, y_dtype for y / dy; gamma, beta,
+ *   scale and the statistics are f32 and all arithmetic is fp32.  C a multiple of 8, C <= 1536, M < 2^31, every tensor dense and
+ *   16-byte aligned.  The mode is which pointers are given:
+ *     norm        branch = s = NULL:  y = LN(x) * gamma + beta, mean_rstd f32 [M, 2] = (mean, 1 / sqrt(var + eps)) per row
+ *     add + norm  branch, s, y:       s = x + scale[row / rows_per_sample] * branch, stored in x's dtype; y = LN(s as stored) ...
+ *     add         branch, s, y = NULL: s only (gamma, beta, mean_rstd unused)
+ *   scale f32 [M / rows_per_sample] or NULL (= 1): the per-sample drop-path factor.  The variance is the biased two-pass form.
+ *   bwd   with g = dy * gamma and x_hat recomputed from the saved s: dLN = rstd * (g - mean_C(g) - x_hat * mean_C(g * x_hat));
+ *         ds = dLN + dsum, where dsum (the gradient of the s output) or dy may be NULL; dx = ds, dbranch = scale * ds, each
+ *         written only when its pointer is given.  dgamma = sum_rows dy * x_hat and dbeta = sum_rows dy (f32 [C]) are produced
+ *         when partial (f32 [parts, 2, C], parts = bfhip_layernorm_parts()), dgamma and dbeta are given, NULL all three
+ *         otherwise: one partial row per workgroup, added by a second small launch in a fixed order.  No atomics: forward and
+ *         backward are run-to-run reproducible.  No allocation, no synchronisation; everything runs on `stream`.
+ *   bfhip_layernorm_supported / _parts are host-only (no device needed); supported answers 0 for a C that is not a multiple of 8
+ *   or exceeds 1536, an M outside [1, 2^31) or a dtype other than 0 / 1.
+ * --------------------------------------------------------------------------------------- */
+int bfhip_layernorm_supported(long long M, int C, int x_dtype, int y_dtype);
+int bfhip_layernorm_parts(long long M, int C);
+int bfhip_layernorm_fwd(const void *x, const void *branch, const float *scale, long long rows_per_sample, const float *gamma,
+                        const float *beta, long long M, int C, float eps, int x_dtype, int branch_dtype, int y_dtype, void *s,
+                        void *y, float *mean_rstd, void *stream);
+int bfhip_layernorm_bwd(const void *s, const float *mean_rstd, const float *gamma, const void *dy, const void *dsum,
+                        const float *scale, long long rows_per_sample, long long M, int C, int x_dtype, int branch_dtype,
+                        int y_dtype, void *dx, void *dbranch, float *partial, int parts, float *dgamma, float *dbeta,
+                        void *stream);
+
 #ifdef __cplusplus
 }
 #endif
