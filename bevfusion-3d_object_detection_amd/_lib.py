@@ -140,6 +140,10 @@ SIGNATURES = {
                             [_c_int] * 3 + [_c_vp] * 4),
     "bfhip_layernorm_bwd": (_c_int, [_c_vp] * 6 + [ctypes.c_longlong, ctypes.c_longlong] + [_c_int] * 4 + [_c_vp] * 3 + [_c_int] +
                             [_c_vp] * 3),
+    "bfhip_bn_eval_supported": (_c_int, [ctypes.c_longlong, _c_int, _c_int]),
+    "bfhip_bn_eval_parts": (_c_int, [ctypes.c_longlong, _c_int, _c_int]),
+    "bfhip_bn_eval_fwd": (_c_int, [_c_vp] * 6 + [ctypes.c_longlong, _c_int, _c_int, ctypes.c_float, _c_int, _c_vp, _c_vp]),
+    "bfhip_bn_eval_bwd": (_c_int, [_c_vp] * 6 + [ctypes.c_longlong, _c_int, _c_int, ctypes.c_float, _c_int] + [_c_vp] * 5),
 }
 
 _lib = None

@@ -1,5 +1,6 @@
 """BatchNorm2d (+ residual) (+ ReLU) for the dense conv stacks, fused in csrc/bn2d.hip when the activation is
-channels-last (the layout MIOpen's NHWC kernels produce) and the module is training.
+channels-last (the layout MIOpen's NHWC kernels produce) and the module is training, and in csrc/bn_eval.hip when the module
+is in eval mode (one pass on the running statistics, forward and backward; BFHIP_BN_EVAL=0 switches that off).
 
 `BatchNorm2dAct` IS an `nn.BatchNorm2d` (same parameters, buffers and state-dict keys as the reference's
 `build_norm_layer(dict(type='BN'))` modules), so checkpoints load unchanged; `bn_act()` returns the
@@ -131,6 +132,116 @@ class _BN2dFunction(torch.autograd.Function):
         return dx, dres, dgb[:C].to(weight.dtype), dgb[C:].to(weight.dtype), None, None, None, None, None, None, None
 
 
+# ----------------------------------------------------------------------------- eval mode (csrc/bn_eval.hip)
+# BatchNorm on its running statistics (+ residual) (+ ReLU) in one pass: inference, `norm_eval`, frozen backbone stages.
+# BFHIP_BN_EVAL switches it; it ships on (measured: DESIGN.md section 6), BFHIP_BN_EVAL=0 selects the torch path, which has the
+# same semantics.
+FUSED_BN_EVAL = os.environ.get("BFHIP_BN_EVAL", "1") != "0"
+EVAL_LAUNCHES = dict(fwd=0, bwd=0)  # kernel calls made so far (tests and tools read the difference)
+_EVAL_OK = {}
+
+
+def _eval_supported(M, C, dt):
+    """bfhip_bn_eval_supported, memoised per shape (host-only)."""
+    key = (M, C, dt)
+    ok = _EVAL_OK.get(key)
+    if ok is None:
+        ok = _EVAL_OK[key] = bool(_lib.load().bfhip_bn_eval_supported(M, C, dt))
+    return ok
+
+
+def _eval_fusable(mod, x):
+    """Does an eval-mode call of BatchNorm module `mod` on x run in csrc/bn_eval.hip?  x is a dense row-major [M, C] matrix in
+    memory: channels-last [N, C, H, W] or contiguous [M, C]."""
+    if not (FUSED_BN_EVAL and not mod.training and mod.track_running_stats and mod.affine and x.is_cuda and x.dtype in _DT
+            and x.dim() in (2, 4) and x.numel() > 0):
+        return False
+    dense = x.is_contiguous(memory_format=torch.channels_last) if x.dim() == 4 else x.is_contiguous()
+    w = mod.weight
+    return (dense and x.data_ptr() % 16 == 0 and w.dtype == torch.float32 and w.device == x.device
+            and _eval_supported(x.numel() // x.shape[1], x.shape[1], _DT[x.dtype]))
+
+
+def _dense_as(t, dtype, dim):
+    """t in `dtype`, dense in the layout the kernels read (channels-last for dim 4, contiguous for dim 2) and 16-byte aligned; a
+    no-op for a tensor that already is."""
+    if t.dtype != dtype:
+        t = t.to(dtype)
+    t = t.contiguous(memory_format=torch.channels_last) if dim == 4 else t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.preserve_format)
+
+
+def _eval_fwd(x, residual, weight, bias, running_mean, running_var, eps, relu):
+    C = x.shape[1]
+    res = _dense_as(residual, x.dtype, x.dim()) if residual is not None else None
+    y = torch.empty_like(x)  # keeps the strides
+    with torch.cuda.device(x.device):
+        _lib.call("bfhip_bn_eval_fwd", x.data_ptr(), _lib.ptr(res), weight.data_ptr(), bias.data_ptr(), running_mean.data_ptr(),
+                  running_var.data_ptr(), x.numel() // C, C, _DT[x.dtype], float(eps), 1 if relu else 0, y.data_ptr(),
+                  _lib.stream_of(x))
+    EVAL_LAUNCHES["fwd"] += 1
+    return y
+
+
+class _BNEvalFunction(torch.autograd.Function):
+    """y = act(BN_eval(x) [+ residual]); x, residual, y dense [M, C] in memory, f32 or bf16."""
+
+    @staticmethod
+    def forward(ctx, x, residual, weight, bias, running_mean, running_var, eps, relu):
+        y = _eval_fwd(x, residual, weight, bias, running_mean, running_var, eps, relu)
+        need = ctx.needs_input_grad
+        ctx.affine = need[2] or need[3]
+        ctx.save_for_backward(x if ctx.affine else None, y if relu else None, weight, running_mean, running_var)
+        ctx.eps, ctx.relu = float(eps), relu
+        ctx.x_dtype, ctx.x_dim = x.dtype, x.dim()
+        ctx.res_dtype = residual.dtype if residual is not None else None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, y, weight, running_mean, running_var = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        want_dx, want_dres, affine = need[0], need[1], ctx.affine
+        if not (want_dx or want_dres or affine):
+            return (None,) * 8
+        dy = _dense_as(dy, ctx.x_dtype, ctx.x_dim)
+        C = dy.shape[1]
+        M, dt = dy.numel() // C, _DT[dy.dtype]
+        dx = torch.empty_like(dy) if want_dx else None
+        dres = None
+        if want_dres:
+            dres = torch.empty_like(dy) if ctx.relu else dy  # without ReLU the residual's gradient IS dy
+        kernel_dres = dres if ctx.relu else None
+        partial = dgb = None
+        if affine:
+            parts = _lib.load().bfhip_bn_eval_parts(M, C, dt)
+            partial = torch.empty((parts, 2, C), dtype=torch.float32, device=dy.device)
+            dgb = torch.empty(2 * C, dtype=torch.float32, device=dy.device)
+        if dx is not None or kernel_dres is not None or affine:
+            with torch.cuda.device(dy.device):
+                _lib.call("bfhip_bn_eval_bwd", dy.data_ptr(), _lib.ptr(y), _lib.ptr(x) if affine else None, weight.data_ptr(),
+                          running_mean.data_ptr(), running_var.data_ptr(), M, C, dt, ctx.eps, 1 if ctx.relu else 0, _lib.ptr(dx),
+                          _lib.ptr(kernel_dres), _lib.ptr(partial), _lib.ptr(dgb), _lib.stream_of(dy))
+            EVAL_LAUNCHES["bwd"] += 1
+        if dres is not None and ctx.res_dtype != dres.dtype:
+            dres = dres.to(ctx.res_dtype)
+        dw = dgb[:C].to(weight.dtype) if need[2] else None
+        db = dgb[C:].to(weight.dtype) if need[3] else None
+        return dx, dres, dw, db, None, None, None, None
+
+
+def eval_apply(mod, x, residual, relu):
+    """The eval-mode forward of BatchNorm module `mod` on the kernels (the caller has checked `_eval_fusable(mod, x)`)."""
+    args = (x, residual, mod.weight, mod.bias, mod.running_mean, mod.running_var, mod.eps, bool(relu))
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in args[:4]):
+        return _BNEvalFunction.apply(*args)
+    return _eval_fwd(*args)
+
+
+def _eval_residual_ok(x, residual):
+    return residual is None or (residual.is_cuda and residual.device == x.device and residual.shape == x.shape)
+
+
 class _LazyBatchCounter:
     """`num_batches_tracked` advanced lazily (it only matters when momentum is None): the per-step `add_(1)` launch of every
     BN layer is folded into a host counter that is flushed into the buffer whenever the state dict is read."""
@@ -162,6 +273,10 @@ class BatchNorm2dAct(_LazyBatchCounter, nn.BatchNorm2d):
                 and x.is_contiguous(memory_format=torch.channels_last)
                 and _ws_bytes(x.numel() // x.shape[1], x.shape[1], _DT[x.dtype]) > 0)
 
+    def eval_fusable(self, x):
+        """Eval mode on the running statistics: does x take csrc/bn_eval.hip (BFHIP_BN_EVAL)?"""
+        return _eval_fusable(self, x)
+
     def forward(self, x, residual=None, relu=None):
         relu = self.act if relu is None else relu
         if self.fusable(x):
@@ -177,6 +292,8 @@ class BatchNorm2dAct(_LazyBatchCounter, nn.BatchNorm2d):
             return _apply(x, residual, self.weight, self.bias, self.running_mean, self.running_var, self.eps, self.momentum,
                           relu, partial)
         self._flush_batches()
+        if self.eval_fusable(x) and x.dim() == 4 and _eval_residual_ok(x, residual):
+            return eval_apply(self, x, residual, relu)
         out = super().forward(x)
         if residual is not None:
             out = out + residual
@@ -189,7 +306,11 @@ class BatchNorm2dAct(_LazyBatchCounter, nn.BatchNorm2d):
 class BatchNormRows(_LazyBatchCounter, nn.BatchNorm1d):
     """nn.BatchNorm1d (same parameters / buffers / state-dict keys) for row-major feature matrices [M, C]: in training on a
     supported width the statistics, the affine map and an optional ReLU run in the fused kernels of csrc/bn2d.hip
-    (an [M, C] matrix is the channels-last view [M, C, 1, 1]).  [B, C, L] inputs take the torch path."""
+    (an [M, C] matrix is the channels-last view [M, C, 1, 1]); in eval mode they run in csrc/bn_eval.hip
+    (BFHIP_BN_EVAL).  [B, C, L] inputs take the torch path."""
+
+    def eval_fusable(self, x):
+        return _eval_fusable(self, x)
 
     def forward(self, x, relu=False):
         if (FUSED_BN2D and self.training and x.is_cuda and x.dim() == 2 and x.dtype in _DT and self.affine
@@ -201,6 +322,8 @@ class BatchNormRows(_LazyBatchCounter, nn.BatchNorm1d):
                        self.momentum, relu)
             return y.view(M, C)
         self._flush_batches()
+        if self.eval_fusable(x) and x.dim() == 2:
+            return eval_apply(self, x, None, relu)
         out = super().forward(x)
         return F.relu(out) if relu else out
 

@@ -1,0 +1,360 @@
+// bn_eval.hip -- BatchNorm on its RUNNING statistics (+ residual add) (+ ReLU) over a dense row-major [M, C] matrix, fwd + bwd
+// (gfx950).  The matrix is a channels-last [N, C, H, W] activation (M = N*H*W) or a feature matrix [M, C].
+//
+// With fixed statistics the layer is a per-channel affine map, so both directions are one elementwise pass:
+//   forward   y = act((x - mean) * a + beta [+ residual]),  a = gamma / sqrt(var + eps)       one launch, no workspace
+//   backward  g = dy * [y > 0] (y is read only with ReLU);  dx = g * a;  dres = g             one launch
+//             dgamma = sum_rows g * x_hat, dbeta = sum_rows g, x_hat = (x - mean) / sqrt(var + eps): one partial row
+//             [2][C] per workgroup, added in a fixed order by a second small launch (no atomics: reruns are bit-identical)
+// All arithmetic is fp32 with one rounding at the store.  The mean is subtracted FIRST: (x - mean) * a has no cancellation
+// between a*x and a*mean, which a precomputed shift b = beta - mean*a would bring in.
+//
+// A thread owns one 16-byte channel vector (8 bf16 / 4 f32) for the whole launch, so its per-channel coefficients are derived
+// once from the four parameter vectors and stay in registers.  The L = C / V vectors of a row belong to L consecutive threads
+// and a workgroup covers R = 256 / L consecutive rows per iteration: one iteration reads R * L * 16 contiguous bytes.  A row
+// of more than 256 vectors (up to 512: 2048 f32 channels) is cut into column tiles of 256 (blockIdx.y), R = 1.  The grid is
+// capped at 2048 workgroups, which stride over the row groups.
+#include "common.h"
+
+namespace bfhip {
+namespace {
+
+typedef unsigned short bf16_t;
+
+constexpr int kBlock = 256;
+constexpr int kMaxVec = 512;     // vectors per row: one thread each, in column tiles of kBlock
+constexpr int kMaxBlocks = 2048;
+constexpr int kMinIters = 4;     // row groups per workgroup before the grid grows
+
+template <typename T> struct Vec;
+template <> struct Vec<float> {
+  static constexpr int V = 4;
+  static __device__ __forceinline__ void load(const float *p, float *o) {
+    const float4 v = *(const float4 *)p;
+    o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
+  }
+  static __device__ __forceinline__ void store(float *p, const float *o) { *(float4 *)p = make_float4(o[0], o[1], o[2], o[3]); }
+};
+template <> struct Vec<bf16_t> {
+  static constexpr int V = 8;
+  static __device__ __forceinline__ void load(const bf16_t *p, float *o) {
+    const uint4 v = *(const uint4 *)p;
+    const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      o[2 * i] = __uint_as_float(w[i] << 16);
+      o[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
+    }
+  }
+  static __device__ __forceinline__ unsigned rne(float f) {  // fp32 -> bf16, round to nearest even (NaN kept quiet)
+    const unsigned u = __float_as_uint(f);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
+    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+  }
+  static __device__ __forceinline__ void store(bf16_t *p, const float *o) {
+    uint4 v;
+    v.x = rne(o[0]) | (rne(o[1]) << 16);
+    v.y = rne(o[2]) | (rne(o[3]) << 16);
+    v.z = rne(o[4]) | (rne(o[5]) << 16);
+    v.w = rne(o[6]) | (rne(o[7]) << 16);
+    *(uint4 *)p = v;
+  }
+};
+
+// V consecutive f32 parameters starting at channel c (a multiple of V; the base is 16-byte aligned)
+template <int V>
+__device__ __forceinline__ void load_param(const float *p, int c, float *o) {
+#pragma unroll
+  for (int i = 0; i < V; i += 4) {
+    const float4 v = *(const float4 *)(p + c + i);
+    o[i] = v.x; o[i + 1] = v.y; o[i + 2] = v.z; o[i + 3] = v.w;
+  }
+}
+
+struct Shape {
+  long long M, groups;  // rows; row groups of R rows
+  int C, L, Lb, R;      // channels; vectors per row; vectors per column tile (blockIdx.y); rows per workgroup iteration
+};
+
+template <typename T, bool RES, bool RELU>
+__global__ __launch_bounds__(kBlock) void bn_eval_fwd_kernel(const T *__restrict__ x, const T *__restrict__ res,
+                                                             const float *__restrict__ gamma, const float *__restrict__ beta,
+                                                             const float *__restrict__ rmean, const float *__restrict__ rvar,
+                                                             float eps, Shape sh, T *__restrict__ y) {
+  constexpr int V = Vec<T>::V;
+  const int t = threadIdx.x, cv = blockIdx.y * sh.Lb + t % sh.Lb, rl = t / sh.Lb;
+  if (rl >= sh.R || cv >= sh.L) return;
+  float a[V], mean[V], b[V];
+  {
+    float var[V];
+    load_param<V>(gamma, cv * V, a);
+    load_param<V>(rvar, cv * V, var);
+    load_param<V>(rmean, cv * V, mean);
+    load_param<V>(beta, cv * V, b);
+#pragma unroll
+    for (int j = 0; j < V; ++j) a[j] *= 1.f / sqrtf(var[j] + eps);
+  }
+  const size_t col = (size_t)cv * V;
+  const long long step = gridDim.x;
+  long long g = blockIdx.x;
+  // two row groups in flight per thread
+  for (; g + step < sh.groups; g += 2 * step) {
+    const long long r0 = g * sh.R + rl, r1 = (g + step) * sh.R + rl;  // r0 < M: only the LAST group can be short
+    const bool ok1 = r1 < sh.M;
+    const size_t o0 = (size_t)r0 * sh.C + col, o1 = (size_t)(ok1 ? r1 : r0) * sh.C + col;
+    float v[2][V], q[2][V];
+    Vec<T>::load(x + o0, v[0]);
+    Vec<T>::load(x + o1, v[1]);
+    if (RES) {
+      Vec<T>::load(res + o0, q[0]);
+      Vec<T>::load(res + o1, q[1]);
+    }
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int j = 0; j < V; ++j) {
+        float o = fmaf(v[u][j] - mean[j], a[j], b[j]);
+        if (RES) o += q[u][j];
+        v[u][j] = (RELU && !(o > 0.f)) ? 0.f : o;
+      }
+    Vec<T>::store(y + o0, v[0]);
+    if (ok1) Vec<T>::store(y + o1, v[1]);
+  }
+  if (g < sh.groups) {
+    const long long r = g * sh.R + rl;
+    if (r < sh.M) {
+      const size_t o0 = (size_t)r * sh.C + col;
+      float v[V], q[V];
+      Vec<T>::load(x + o0, v);
+      if (RES) Vec<T>::load(res + o0, q);
+#pragma unroll
+      for (int j = 0; j < V; ++j) {
+        float o = fmaf(v[j] - mean[j], a[j], b[j]);
+        if (RES) o += q[j];
+        v[j] = (RELU && !(o > 0.f)) ? 0.f : o;
+      }
+      Vec<T>::store(y + o0, v);
+    }
+  }
+}
+
+// dx and dres are written where their pointer is given (uniform over the launch).  AFF: also accumulate this workgroup's
+// partial row [2][C] = (sum g * x_hat, sum g) over its rows.
+template <typename T, bool RELU, bool AFF>
+__global__ __launch_bounds__(kBlock) void bn_eval_bwd_kernel(const T *__restrict__ dy, const T *__restrict__ y,
+                                                             const T *__restrict__ x, const float *__restrict__ gamma,
+                                                             const float *__restrict__ rmean, const float *__restrict__ rvar,
+                                                             float eps, Shape sh, T *__restrict__ dx, T *__restrict__ dres,
+                                                             float *__restrict__ partial) {
+  constexpr int V = Vec<T>::V;
+  __shared__ float sm[AFF ? 2 * kBlock * V : 1];
+  const int t = threadIdx.x, cv = blockIdx.y * sh.Lb + t % sh.Lb, rl = t / sh.Lb;
+  const bool live = rl < sh.R && cv < sh.L;
+  float s0[V], s1[V];
+#pragma unroll
+  for (int j = 0; j < V; ++j) s0[j] = s1[j] = 0.f;
+  if (live) {
+    float a[V], mean[V], rstd[V];
+#pragma unroll
+    for (int j = 0; j < V; ++j) a[j] = mean[j] = rstd[j] = 0.f;
+    if (dx || AFF) {
+      load_param<V>(rvar, cv * V, rstd);
+#pragma unroll
+      for (int j = 0; j < V; ++j) rstd[j] = 1.f / sqrtf(rstd[j] + eps);
+    }
+    if (dx) {
+      load_param<V>(gamma, cv * V, a);
+#pragma unroll
+      for (int j = 0; j < V; ++j) a[j] *= rstd[j];
+    }
+    if (AFF) load_param<V>(rmean, cv * V, mean);
+    const size_t col = (size_t)cv * V;
+    for (long long g = blockIdx.x; g < sh.groups; g += gridDim.x) {
+      const long long r = g * sh.R + rl;
+      if (r >= sh.M) break;  // only the last group can be short
+      const size_t o = (size_t)r * sh.C + col;
+      float gv[V], yv[V], xv[V];
+      Vec<T>::load(dy + o, gv);
+      if (RELU) Vec<T>::load(y + o, yv);
+      if (AFF) Vec<T>::load(x + o, xv);
+      if (RELU) {
+#pragma unroll
+        for (int j = 0; j < V; ++j)
+          if (!(yv[j] > 0.f)) gv[j] = 0.f;
+      }
+      if (dres) Vec<T>::store(dres + o, gv);
+      if (AFF) {
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+          s0[j] = fmaf(gv[j], (xv[j] - mean[j]) * rstd[j], s0[j]);
+          s1[j] += gv[j];
+        }
+      }
+      if (dx) {
+#pragma unroll
+        for (int j = 0; j < V; ++j) gv[j] *= a[j];
+        Vec<T>::store(dx + o, gv);
+      }
+    }
+  }
+  if (AFF) {
+    // the R row lanes of a channel add in turn (fixed order), then one coalesced store of this column tile's piece of the
+    // partial row.  Local channel cl (of the tile) of row lane rl lives at sm[rl * Lb * V + cl]
+    float *m0 = sm, *m1 = sm + kBlock * V;
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      m0[t * V + j] = s0[j];
+      m1[t * V + j] = s1[j];
+    }
+    __syncthreads();
+    const int nl = sh.Lb * V, c0 = blockIdx.y * nl;
+    float *dst = partial + (size_t)blockIdx.x * 2 * sh.C + c0;
+    for (int cl = t; cl < nl && c0 + cl < sh.C; cl += kBlock) {
+      float p0 = 0.f, p1 = 0.f;
+      for (int k = 0; k < sh.R; ++k) {
+        p0 += m0[k * nl + cl];
+        p1 += m1[k * nl + cl];
+      }
+      dst[cl] = p0;
+      dst[sh.C + cl] = p1;
+    }
+  }
+}
+
+// dgb[col] = sum over the partial rows, in a fixed order: thread (cx, py) adds rows py, py + 4, ..; the four row lanes then add in turn
+__global__ __launch_bounds__(kBlock) void bn_eval_param_grad_kernel(const float *__restrict__ partial, int parts, int C2,
+                                                                    float *__restrict__ dgb) {
+  constexpr int kRows = kBlock / kWave;
+  __shared__ float red[kRows][kWave];
+  const int cx = threadIdx.x & (kWave - 1), py = threadIdx.x / kWave;
+  const int col = blockIdx.x * kWave + cx;
+  float acc = 0.f;
+  if (col < C2)
+    for (int p = py; p < parts; p += kRows) acc += partial[(size_t)p * C2 + col];
+  red[py][cx] = acc;
+  __syncthreads();
+  if (py == 0 && col < C2) dgb[col] = ((red[0][cx] + red[1][cx]) + red[2][cx]) + red[3][cx];
+}
+
+inline int elem_size(int dtype) { return dtype == 1 ? 2 : 4; }
+
+inline bool shape_ok(long long M, int C, int dtype) {
+  if (dtype != 0 && dtype != 1) return false;
+  const int V = 16 / elem_size(dtype);
+  return M >= 1 && M <= 0x7fffffffll && C >= V && C % V == 0 && C / V <= kMaxVec;
+}
+
+inline Shape make_shape(long long M, int C, int dtype) {
+  Shape sh;
+  sh.M = M;
+  sh.C = C;
+  sh.L = C / (16 / elem_size(dtype));
+  sh.Lb = sh.L < kBlock ? sh.L : kBlock;
+  sh.R = kBlock / sh.Lb;
+  sh.groups = (M + sh.R - 1) / sh.R;
+  return sh;
+}
+
+inline int col_tiles(const Shape &sh) { return (sh.L + sh.Lb - 1) / sh.Lb; }
+
+// every workgroup walks the same number of row groups (the last one may be one short), at least kMinIters where M allows
+inline int grid_for(const Shape &sh, long long cap) {
+  cap = cap / col_tiles(sh) > 0 ? cap / col_tiles(sh) : 1;
+  long long blocks = (sh.groups + kMinIters - 1) / kMinIters;
+  if (blocks > cap) blocks = cap;
+  if (blocks < 1) blocks = 1;
+  const long long iters = (sh.groups + blocks - 1) / blocks;
+  return (int)((sh.groups + iters - 1) / iters);
+}
+
+// workgroups of a backward that produces parameter gradients = rows of `partial`: the partial rows stay below a quarter of
+// one activation tensor (the launch moves three or four of them)
+inline int parts_for(const Shape &sh, int dtype) {
+  long long cap = sh.M * elem_size(dtype) / 32;
+  if (cap < 1) cap = 1;
+  if (cap > kMaxBlocks) cap = kMaxBlocks;
+  return grid_for(sh, cap);
+}
+
+inline bool aligned16(const void *p) { return ((uintptr_t)p % 16) == 0; }
+
+template <typename T>
+void launch_fwd(const void *x, const void *res, const float *gamma, const float *beta, const float *rmean, const float *rvar,
+                float eps, const Shape &sh, int relu, void *y, hipStream_t s) {
+  const dim3 grid(grid_for(sh, kMaxBlocks), col_tiles(sh));
+#define BFHIP_BN_EVAL_FWD(RES, RELU)                                                                                   \
+  hipLaunchKernelGGL((bn_eval_fwd_kernel<T, RES, RELU>), grid, dim3(kBlock), 0, s, (const T *)x, (const T *)res, gamma, \
+                     beta, rmean, rvar, eps, sh, (T *)y)
+  if (res) { if (relu) BFHIP_BN_EVAL_FWD(true, true); else BFHIP_BN_EVAL_FWD(true, false); }
+  else { if (relu) BFHIP_BN_EVAL_FWD(false, true); else BFHIP_BN_EVAL_FWD(false, false); }
+#undef BFHIP_BN_EVAL_FWD
+}
+
+template <typename T>
+void launch_bwd(const void *dy, const void *y, const void *x, const float *gamma, const float *rmean, const float *rvar,
+                float eps, const Shape &sh, int relu, void *dx, void *dres, float *partial, int grid_x, hipStream_t s) {
+  const dim3 grid(grid_x, col_tiles(sh));
+#define BFHIP_BN_EVAL_BWD(RELU, AFF)                                                                                  \
+  hipLaunchKernelGGL((bn_eval_bwd_kernel<T, RELU, AFF>), grid, dim3(kBlock), 0, s, (const T *)dy, (const T *)y,        \
+                     (const T *)x, gamma, rmean, rvar, eps, sh, (T *)dx, (T *)dres, partial)
+  if (partial) { if (relu) BFHIP_BN_EVAL_BWD(true, true); else BFHIP_BN_EVAL_BWD(false, true); }
+  else { if (relu) BFHIP_BN_EVAL_BWD(true, false); else BFHIP_BN_EVAL_BWD(false, false); }
+#undef BFHIP_BN_EVAL_BWD
+}
+
+}  // namespace
+}  // namespace bfhip
+
+using namespace bfhip;
+
+BFHIP_EXPORT int bfhip_bn_eval_supported(long long M, int C, int dtype) { return shape_ok(M, C, dtype) ? 1 : 0; }
+
+BFHIP_EXPORT int bfhip_bn_eval_parts(long long M, int C, int dtype) {
+  return shape_ok(M, C, dtype) ? parts_for(make_shape(M, C, dtype), dtype) : 0;
+}
+
+BFHIP_EXPORT int bfhip_bn_eval_fwd(const void *x, const void *residual, const float *gamma, const float *beta,
+                                   const float *running_mean, const float *running_var, long long M, int C, int dtype, float eps,
+                                   int relu, void *y, void *stream) {
+  BFHIP_REQUIRE(shape_ok(M, C, dtype), "bn_eval_fwd: unsupported M=%lld C=%d dtype=%d", M, C, dtype);
+  BFHIP_REQUIRE(x && y && gamma && beta && running_mean && running_var,
+                "bn_eval_fwd: x, y, gamma, beta and the running statistics are required");
+  BFHIP_REQUIRE(aligned16(x) && aligned16(residual) && aligned16(y) && aligned16(gamma) && aligned16(beta) &&
+                    aligned16(running_mean) && aligned16(running_var),
+                "bn_eval_fwd: tensors must be 16-byte aligned");
+  const Shape sh = make_shape(M, C, dtype);
+  if (dtype == 1)
+    launch_fwd<bf16_t>(x, residual, gamma, beta, running_mean, running_var, eps, sh, relu, y, (hipStream_t)stream);
+  else
+    launch_fwd<float>(x, residual, gamma, beta, running_mean, running_var, eps, sh, relu, y, (hipStream_t)stream);
+  return check_launch("bn_eval_fwd");
+}
+
+BFHIP_EXPORT int bfhip_bn_eval_bwd(const void *dy, const void *y, const void *x, const float *gamma, const float *running_mean,
+                                   const float *running_var, long long M, int C, int dtype, float eps, int relu, void *dx,
+                                   void *dres, float *partial, float *dgb, void *stream) {
+  BFHIP_REQUIRE(shape_ok(M, C, dtype), "bn_eval_bwd: unsupported M=%lld C=%d dtype=%d", M, C, dtype);
+  BFHIP_REQUIRE(dy, "bn_eval_bwd: dy is required");
+  BFHIP_REQUIRE(!relu || y, "bn_eval_bwd: the ReLU mask needs y");
+  BFHIP_REQUIRE((x != nullptr) == (partial != nullptr) && (x != nullptr) == (dgb != nullptr),
+                "bn_eval_bwd: x, partial and dgb are given together or not at all");
+  BFHIP_REQUIRE(dx || dres || partial, "bn_eval_bwd: no output requested");
+  BFHIP_REQUIRE(!dx || (gamma && running_var), "bn_eval_bwd: dx needs gamma and running_var");
+  BFHIP_REQUIRE(!partial || (running_mean && running_var), "bn_eval_bwd: the parameter gradients need the running statistics");
+  BFHIP_REQUIRE(aligned16(dy) && aligned16(y) && aligned16(x) && aligned16(dx) && aligned16(dres) && aligned16(gamma) &&
+                    aligned16(running_mean) && aligned16(running_var) && aligned16(partial) && aligned16(dgb),
+                "bn_eval_bwd: tensors must be 16-byte aligned");
+  const Shape sh = make_shape(M, C, dtype);
+  const int grid = partial ? parts_for(sh, dtype) : grid_for(sh, kMaxBlocks);
+  if (dtype == 1)
+    launch_bwd<bf16_t>(dy, relu ? y : nullptr, x, gamma, running_mean, running_var, eps, sh, relu, dx, dres, partial, grid,
+                       (hipStream_t)stream);
+  else
+    launch_bwd<float>(dy, relu ? y : nullptr, x, gamma, running_mean, running_var, eps, sh, relu, dx, dres, partial, grid,
+                      (hipStream_t)stream);
+  int rc = check_launch("bn_eval_bwd");
+  if (rc != BFHIP_OK || !partial) return rc;
+  hipLaunchKernelGGL(bn_eval_param_grad_kernel, dim3(ceil_div(2 * C, kWave)), dim3(kBlock), 0, (hipStream_t)stream,
+                     (const float *)partial, grid, 2 * C, dgb);
+  return check_launch("bn_eval_param_grad");
+}

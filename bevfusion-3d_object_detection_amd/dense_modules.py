@@ -154,11 +154,21 @@ class MaxPool3x3s2(nn.MaxPool2d):
 
 @MODELS.register_module()
 class ResNet50(nn.Module):
-    """Standard ResNet-50; returns the stride-8/16/32 maps (512, 1024, 2048 channels)."""
+    """Standard ResNet-50; returns the stride-8/16/32 maps (512, 1024, 2048 channels).
 
-    def __init__(self, out_indices=(1, 2, 3)):
+    `frozen_stages` and `norm_eval` follow mmdet 3.x's ResNet (`_freeze_stages` and `train()`, written from knowledge of that
+    package: parity unpinned).  frozen_stages >= 0 puts the stem (conv1, bn1) in eval mode with `requires_grad` off, and
+    `layer1 .. layer{frozen_stages}` likewise; norm_eval keeps every BatchNorm of the backbone on its running statistics while
+    the rest trains (their affine parameters stay trainable outside the frozen stages).  `train()` re-applies both.  The
+    defaults (-1, False) freeze nothing; mmdet's own default is norm_eval=True."""
+
+    def __init__(self, out_indices=(1, 2, 3), frozen_stages=-1, norm_eval=False):
         super().__init__()
+        if not -1 <= frozen_stages <= 4:
+            raise ValueError("frozen_stages must be in [-1, 4], got %r" % (frozen_stages,))
         self.out_indices = out_indices
+        self.frozen_stages = frozen_stages
+        self.norm_eval = norm_eval
         self.conv1 = nn.Conv2d(3, 64, 7, stride=2, padding=3, bias=False)
         self.bn1 = BatchNorm2dAct(64)
         self.relu = nn.ReLU(inplace=True)
@@ -168,6 +178,24 @@ class ResNet50(nn.Module):
         self.layer2 = self._make_layer(128, 4, 2)
         self.layer3 = self._make_layer(256, 6, 2)
         self.layer4 = self._make_layer(512, 3, 2)
+        self._freeze_stages()
+
+    def _freeze_stages(self):
+        frozen = [self.conv1, self.bn1] if self.frozen_stages >= 0 else []
+        frozen += [getattr(self, "layer%d" % i) for i in range(1, self.frozen_stages + 1)]
+        for m in frozen:
+            m.eval()
+            for p in m.parameters():
+                p.requires_grad = False
+
+    def train(self, mode=True):
+        super().train(mode)
+        self._freeze_stages()
+        if mode and self.norm_eval:
+            for m in self.modules():
+                if isinstance(m, nn.modules.batchnorm._BatchNorm):
+                    m.eval()
+        return self
 
     def _make_layer(self, planes, blocks, stride):
         down = None

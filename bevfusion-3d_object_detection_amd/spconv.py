@@ -618,6 +618,10 @@ class BatchNorm1dAct(nn.BatchNorm1d):
         if rows_dev is not None:
             raise RuntimeError("capacity-sized feature matrices need the fused BatchNorm kernels (training mode, supported width)")
         self._flush_batches()
+        if not self.training and x.dim() == 2:
+            from . import bn2d
+            if bn2d._eval_fusable(self, x) and bn2d._eval_residual_ok(x, residual):
+                return bn2d.eval_apply(self, x, residual, relu)  # running statistics: csrc/bn_eval.hip (BFHIP_BN_EVAL)
         out = super().forward(x)
         if residual is not None:
             out = out + residual

@@ -649,6 +649,30 @@ int bfhip_layernorm_bwd(const void *s, const float *mean_rstd, const float *gamm
                         int y_dtype, void *dx, void *dbranch, float *partial, int parts, float *dgamma, float *dbeta,
                         void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Eval-mode BatchNorm (+ residual add) (+ ReLU) over a dense row-major [M, C] matrix (csrc/bn_eval.hip): BatchNorm on its
+ *   RUNNING statistics -- inference, mmdet's norm_eval, frozen backbone stages -- for a channels-last [N, C, H, W] activation
+ *   (M = N*H*W) or a feature matrix [M, C].
+ *   dtype: 0 = f32, 1 = bf16 (x, residual, y, dy, dx, dres share it); gamma, beta and the running statistics are f32 and are
+ *   only read.  C must be a multiple of the 16-byte vector (4 f32 / 8 bf16) with at most 512 vectors per row, M in [1, 2^31)
+ *   (M = 1 is legal: there are no batch statistics): bfhip_bn_eval_supported() tells.  All arithmetic is fp32, one rounding
+ *   at the store.
+ *   fwd   y = act((x - running_mean) * a + beta [+ residual]), a = gamma / sqrt(running_var + eps); one launch, no workspace.
+ *   bwd   g = dy * [y > 0] with relu (y is read only then and may be NULL otherwise), g = dy without; dx = g * a and dres = g,
+ *         each written only when its pointer is given.  dgb f32[2C] <- (dgamma, dbeta) = (sum_rows g * x_hat, sum_rows g) with
+ *         x_hat = (x - running_mean) / sqrt(running_var + eps) when x, partial (f32 [bfhip_bn_eval_parts()][2][C]) and dgb are
+ *         given, NULL all three otherwise: one partial row per workgroup, added by a second small launch in a fixed order.  No
+ *         atomics: run-to-run reproducible.  No allocation, no synchronisation; everything runs on `stream`.
+ *   bfhip_bn_eval_supported / _parts are host-only (no device needed).
+ * --------------------------------------------------------------------------------------- */
+int bfhip_bn_eval_supported(long long M, int C, int dtype);
+int bfhip_bn_eval_parts(long long M, int C, int dtype);
+int bfhip_bn_eval_fwd(const void *x, const void *residual, const float *gamma, const float *beta, const float *running_mean,
+                      const float *running_var, long long M, int C, int dtype, float eps, int relu, void *y, void *stream);
+int bfhip_bn_eval_bwd(const void *dy, const void *y, const void *x, const float *gamma, const float *running_mean,
+                      const float *running_var, long long M, int C, int dtype, float eps, int relu, void *dx, void *dres,
+                      float *partial, float *dgb, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
