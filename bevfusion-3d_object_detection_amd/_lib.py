@@ -128,6 +128,7 @@ SIGNATURES = {
     "bfhip_adamw_segment_bytes": (_c_int, []),
     "bfhip_adamw_chunk_elems": (_c_int, []),
     "bfhip_adamw_step": (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp] + [ctypes.c_float] * 6 + [_c_vp]),
+    "bfhip_adamw_step_groups": (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_int, ctypes.c_float, _c_vp]),
     "bfhip_query_losses": (_c_int, [_c_vp] * 7 + [_c_int] * 6 + [ctypes.c_float, ctypes.c_float] + [_c_vp] * 4),
     "bfhip_swin_attn_supported": (_c_int, [_c_int] * 7),
     "bfhip_swin_attn_parts": (_c_int, [_c_int] * 4),

@@ -582,7 +582,9 @@ int bfhip_bn2d_bwd_mask(const void *dy, const void *x, const unsigned char *relu
  *   (replaces, in the benchmarked training step, clip_grad_norm_ + torch.optim.AdamW of the reference's optim_wrapper,
  *   projects/BEVFusion/configs/nuscenes/bevfusion_lidar_voxel0075_second_secfpn_8xb4-cyclic-20e_nus-3d.py:369-372)
  *   segs_dev      : n_tensors records of bfhip_adamw_segment_bytes() bytes each:
- *                   { float *master, *m, *v; uint16_t *lowp (bf16 copy or NULL); int64 n; int32 grad_bf16, pad }
+ *                   { float *master, *m, *v; uint16_t *lowp (bf16 copy or NULL); int64 n; int32 grad_bf16, group }
+ *                   (group: row of the group table of bfhip_adamw_step_groups, 0 = the single group; ignored by
+ *                   bfhip_adamw_step)
  *   grad_ptrs_dev : int64[n_tensors] device addresses of this step's gradients (0: no gradient = zero gradient), element
  *                   order = the parameter's own memory order
  *   chunks_dev    : int32[n_chunks][2] = (tensor, chunk index) covering every tensor in chunks of bfhip_adamw_chunk_elems()
@@ -595,6 +597,25 @@ int bfhip_adamw_chunk_elems(void);
 int bfhip_adamw_step(const void *segs_dev, const int64_t *grad_ptrs_dev, const int32_t *chunks_dev, int n_chunks,
                      float *partial_dev, float *scalars_dev, float lr, float beta1, float beta2, float eps,
                      float weight_decay, float max_norm, void *stream);
+/* ---------------------------------------------------------------------------------------
+ * the same step with parameter groups and per-step hyper-parameters (mmengine's paramwise_cfg: a smaller lr for the backbone,
+ *   no weight decay on norms and biases; the reference's LinearLR / CosineAnnealingLR / CosineAnnealingMomentum schedules,
+ *   projects/BEVFusion/configs/nuscenes/bevfusion_lidar_voxel0075_second_secfpn_8xb4-cyclic-20e_nus-3d.py:328-372)
+ *   segs_dev, grad_ptrs_dev, chunks_dev, partial_dev, scalars_dev, max_norm : as bfhip_adamw_step; a tensor's `group` field
+ *                   selects its record.  After the call also scalars[6] = 1 if some tensor named a group >= n_groups (that
+ *                   tensor was not updated; nothing is read past the table)
+ *   groups_dev    : f32[n_groups][8] device records; the caller writes [0] lr, [1] beta1, [2] beta2, [3] eps, [4] weight_decay
+ *                   before every call (stream-ordered, e.g. in the same upload as grad_ptrs_dev); the call fills
+ *                   [5] 1 - beta1^step and [6] sqrt(1 - beta2^step); [7] unused
+ *   groups_host   : the same n_groups records in host memory, read during the call only: every group is checked here
+ *                   (lr >= 0, 0 <= beta < 1, eps > 0; BFHIP_E_INVALID names the group), no device read
+ *   The gradient norm, the clip scale, found_inf and the step counter (scalars[2]) are global, over all groups, as
+ *   clip_grad_norm_ over all parameters.  Three launches.  With n_groups = 1 the results are bit-identical to bfhip_adamw_step
+ *   with the same values by value.
+ * --------------------------------------------------------------------------------------- */
+int bfhip_adamw_step_groups(const void *segs_dev, const int64_t *grad_ptrs_dev, const int32_t *chunks_dev, int n_chunks,
+                            float *partial_dev, float *scalars_dev, float *groups_dev, const float *groups_host, int n_groups,
+                            float max_norm, void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * Shifted-window multi-head self-attention of the Swin image backbone (csrc/swin_attn.hip; the reference's camera configs build
