@@ -145,7 +145,15 @@ SIGNATURES = {
     "bfhip_bn_eval_parts": (_c_int, [ctypes.c_longlong, _c_int, _c_int]),
     "bfhip_bn_eval_fwd": (_c_int, [_c_vp] * 6 + [ctypes.c_longlong, _c_int, _c_int, ctypes.c_float, _c_int, _c_vp, _c_vp]),
     "bfhip_bn_eval_bwd": (_c_int, [_c_vp] * 6 + [ctypes.c_longlong, _c_int, _c_int, ctypes.c_float, _c_int] + [_c_vp] * 5),
+    "bfhip_img_preprocess_max_samples": (_c_int, []),
+    "bfhip_img_preprocess": (_c_int, [_c_vp] + [_c_int] * 5 + [_c_vp, _c_vp, ctypes.c_float, _c_int, _c_int, _c_int, _c_int,
+                                      _c_vp, _c_vp]),
 }
+
+
+class ImgDesc(ctypes.Structure):
+    """bfhip_img_desc: one sample of bfhip_img_preprocess, a dense device block [views, 3, h, w]."""
+    _fields_ = [("data", _c_vp), ("h", _c_int), ("w", _c_int)]
 
 _lib = None
 

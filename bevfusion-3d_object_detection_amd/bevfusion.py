@@ -19,6 +19,7 @@ from .ops import Voxelization
 from .ops.voxel import voxel_layer
 from .registry import MODELS
 from . import dense_modules, depth_lss, sparse_encoder, swin  # noqa: F401  (register the module names)
+from .data_preprocessor import Det3DDataPreprocessor
 
 
 def voxel_mean(voxels, num_points):
@@ -47,6 +48,10 @@ class BEVFusion(nn.Module):
         if isinstance(voxelize_cfg.get("max_voxels"), list):
             voxelize_cfg["max_voxels"] = tuple(voxelize_cfg["max_voxels"])
         self.pts_voxel_layer = Voxelization(**voxelize_cfg)
+        # the rest of the dict is the image side (mean / std, size divisor, channel swap): a dict without `mean` only casts and
+        # stacks.  Nothing calls it implicitly: preprocess() / test_step() / val_step() do
+        pre = {k: v for k, v in data_preprocessor.items() if k not in ("voxelize_cfg", "voxelize_reduce", "type")}
+        self.data_preprocessor = Det3DDataPreprocessor(**pre)
         # pts_voxel_encoder (HardSimpleVFE) is built but never called by the reference (:52, reduce is inline)
         build = lambda cfg: MODELS.build(cfg) if cfg is not None else None
         self.img_backbone = build(img_backbone)
@@ -237,7 +242,9 @@ class BEVFusion(nn.Module):
                     mats[key] = batch_inputs_dict[key]
                 else:
                     default = np.eye(4) if "aug" in key else None
-                    mats[key] = imgs.new_tensor(np.asarray([m.get(meta_key, default) for m in batch_input_metas]))
+                    # fp32 whatever the images are (a bf16 batch from the data preprocessor must not narrow the calibration)
+                    mats[key] = imgs.new_tensor(np.asarray([m.get(meta_key, default) for m in batch_input_metas]),
+                                                dtype=torch.float32)
             prepared = None
             if overlap and self.side_prepare and hasattr(self.view_transform, "prepare"):
                 # the part of the view transform that needs no image features -- sparse depth images, GT depth histogram, BEV plan,
@@ -323,6 +330,20 @@ class BEVFusion(nn.Module):
         feats, _ = self.extract_feat(batch_inputs_dict, metas)
         return self.bbox_head.predict(feats, metas)
 
+    # ------------------------------------------------------------------ mmengine's BaseModel entry points
+    def preprocess(self, data, training=False):
+        """Raw batch of the data pipeline ({"inputs": {"points", "img"}, "data_samples"}) -> what forward / loss / predict
+        take: {"inputs": {"points", "imgs"}, "data_samples"} on the model's device (data_preprocessor.Det3DDataPreprocessor)."""
+        return self.data_preprocessor(data, training)
+
+    def test_step(self, data):
+        """mmengine BaseModel.test_step: predict() on the preprocessed batch; the calibration matrices come from the samples'
+        metainfo, as in predict()."""
+        data = self.preprocess(data, False)
+        return self.predict(data["inputs"], data["data_samples"])
+
+    val_step = test_step
+
     @staticmethod
     def parse_losses(losses):
         """BF/bevfusion.py:88-121: -> (loss, log_vars).  Every entry is reduced to its mean (lists of tensors: sum of the
@@ -362,7 +383,8 @@ def nuscenes_config(camera=True, lidar=True, img_backbone="resnet50"):
     assert img_backbone in ("resnet50", "swin_t"), img_backbone
     cfg = dict(
         type="BEVFusion",
-        data_preprocessor=dict(voxelize_cfg=dict(max_num_points=10, point_cloud_range=[-54.0, -54.0, -5.0, 54.0, 54.0, 3.0],
+        data_preprocessor=dict(pad_size_divisor=32,
+                               voxelize_cfg=dict(max_num_points=10, point_cloud_range=[-54.0, -54.0, -5.0, 54.0, 54.0, 3.0],
                                                  voxel_size=[0.075, 0.075, 0.2], max_voxels=[120000, 160000],
                                                  voxelize_reduce=True)),
         pts_backbone=dict(type="SECOND", in_channels=256, out_channels=[128, 256], layer_nums=[5, 5],
@@ -402,6 +424,8 @@ def nuscenes_config(camera=True, lidar=True, img_backbone="resnet50"):
             encoder_channels=((16, 16, 32), (32, 32, 64), (64, 64, 128), (128, 128)),
             encoder_paddings=((0, 0, 1), (0, 0, 1), (0, 0, (1, 1, 0)), (0, 0)), block_type="basicblock")
     if camera:
+        # the camera config's image normalisation (...lidar-cam...py:10-14), consumed by data_preprocessor.Det3DDataPreprocessor
+        cfg["data_preprocessor"].update(mean=[123.675, 116.28, 103.53], std=[58.395, 57.12, 57.375], bgr_to_rgb=False)
         cfg["img_backbone"] = dict(type="ResNet50")
         cfg["img_neck"] = dict(type="GeneralizedLSSFPN", in_channels=[512, 1024, 2048], out_channels=256, start_level=0,
                                num_outs=3, upsample_cfg=dict(mode="bilinear", align_corners=False))
@@ -426,10 +450,9 @@ def custom_data_config(camera=True, lidar=True):
     (projects/BEVFusion/configs/custom_data/lidar_custom.py:38-146 and lidar-cam_custom.py:9-59): five cameras of 384 x 704
     pixels (48 x 88 feature maps), three point features, the five CUSTOM_CLASSES, 500 proposals, velocity code weights 0 and
     the Swin-T image backbone.  tests/golden/custom_data_model_cfg.json holds the reference's merged dict; the keys left out
-    here (norm / act / conv cfgs our modules fix, init_cfg, the data preprocessor's mean / std, unused type names) are
+    here (norm / act / conv cfgs our modules fix, init_cfg, unused type names) are
     listed in tests/test_custom_config_cpu.py."""
     cfg = nuscenes_config(camera=camera, lidar=lidar, img_backbone="swin_t")
-    cfg["data_preprocessor"]["pad_size_divisor"] = 32
     cfg["pts_voxel_encoder"] = dict(type="HardSimpleVFE", num_features=3)
     head = cfg["bbox_head"]
     head["num_proposals"] = 500
@@ -438,7 +461,6 @@ def custom_data_config(camera=True, lidar=True):
     if lidar:
         cfg["pts_middle_encoder"]["in_channels"] = 3
     if camera:
-        cfg["data_preprocessor"]["bgr_to_rgb"] = False
         cfg["img_backbone"].pop("init_cfg")  # the fork points at a checkpoint on its author's disk
         cfg["view_transform"]["image_size"] = [384, 704]
         cfg["view_transform"]["feature_size"] = [48, 88]

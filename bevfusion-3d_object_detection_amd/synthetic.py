@@ -169,6 +169,17 @@ def camera_rig(batch=1, seed=None, train_aug=False, num_cams=6, resize=0.48, cro
     return out
 
 
+def camera_images_u8(batch=1, views=NUSC["num_cams"], h=NUSC["image_size"][0], w=NUSC["image_size"][1], seed=2000):
+    """Raw camera frames as the data pipeline delivers them to the data preprocessor: u8[batch, views, 3, h, w] with values
+    over the whole 0..255 range -- a smooth per-view gradient (sky to road) plus seeded pixel noise, so that neighbouring
+    pixels, channels and views all differ."""
+    rng = np.random.default_rng(seed)
+    ramp = np.linspace(200.0, 40.0, h, dtype=np.float32)[:, None] + np.linspace(-30.0, 30.0, w, dtype=np.float32)[None, :]
+    tint = rng.uniform(-25.0, 25.0, (batch, views, 3, 1, 1)).astype(np.float32)
+    noise = rng.integers(-48, 49, (batch, views, 3, h, w)).astype(np.float32)
+    return np.clip(ramp + tint + noise, 0.0, 255.0).astype(np.uint8)
+
+
 def create_frustum(image_size=NUSC["image_size"], feature_size=NUSC["feature_size"], dbound=NUSC["dbound"]):
     """(D, fH, fW, 3) pixel-depth grid (BF/depth_lss.py:53-66): xs/ys = linspace over the image,
     ds = arange(dbound) -- evaluated in fp32 like torch.arange/linspace(dtype=float)."""

@@ -694,6 +694,32 @@ int bfhip_bn_eval_bwd(const void *dy, const void *y, const void *x, const float 
                       const float *running_var, long long M, int C, int dtype, float eps, int relu, void *dx, void *dres,
                       float *partial, float *dgb, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Camera-image preprocessing (csrc/preprocess.hip): the image path of the reference's Det3DDataPreprocessor
+ *   (M3D/models/data_preprocessors/data_preprocessor.py:126-330: channel swap, .float(), (x - mean) / std, pad to the size
+ *   divisor at the bottom and right, stack) in one pass that also writes the dtype and memory format the backbone reads.
+ *   samples_host: n_samples descriptors in HOST memory; sample i is a dense DEVICE block [views, 3, h_i, w_i] of raw pixel
+ *     values, src_dtype 0 = uint8, 1 = float32 (one dtype and one view count for all samples; h and w may differ).  The
+ *     descriptors travel in the kernel arguments, bfhip_img_preprocess_max_samples() per launch; a longer list is cut into
+ *     that many launches.  No device table, no copy.
+ *   out[b, v, c, y, x] = (float(src_b[v, c', y, x]) - mean_host[c]) / std_host[c] inside the image (c' = 2 - c with swap_rb, else
+ *     c; with normalise = 0 just the float value, mean_host / std_host may be NULL) and pad_value itself outside (y >= h_b or
+ *     x >= w_b).  fp32 arithmetic in that order with a true division: bit-identical to the IEEE result.  out_dtype 0 = f32,
+ *     1 = bf16 (that fp32 value rounded to nearest even once).  Hp >= max h and Wp >= max w, or BFHIP_E_INVALID.
+ *   out layout: pixel_major = 0: [n_samples, views, 3, Hp, Wp] contiguous; 1: [n_samples * views, Hp, Wp, 3] (the storage of
+ *     a channels-last [n_samples * views, 3, Hp, Wp] tensor).  Every element of out is written exactly once, padding included.
+ *     16-byte stores are used when Wp is a multiple of 8 and out is 16-byte aligned; any other Wp or alignment is legal.
+ *   No allocation, no synchronisation; everything runs on `stream`.
+ * --------------------------------------------------------------------------------------- */
+typedef struct bfhip_img_desc {
+  const void *data; /* device pointer of the [views, 3, h, w] block */
+  int h, w;
+} bfhip_img_desc;
+int bfhip_img_preprocess_max_samples(void);
+int bfhip_img_preprocess(const bfhip_img_desc *samples_host, int n_samples, int views, int src_dtype, int swap_rb, int normalise,
+                         const float *mean_host, const float *std_host, float pad_value, int Hp, int Wp, int out_dtype,
+                         int pixel_major, void *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
