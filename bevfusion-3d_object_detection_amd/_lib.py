@@ -148,6 +148,11 @@ SIGNATURES = {
     "bfhip_img_preprocess_max_samples": (_c_int, []),
     "bfhip_img_preprocess": (_c_int, [_c_vp] + [_c_int] * 5 + [_c_vp, _c_vp, ctypes.c_float, _c_int, _c_int, _c_int, _c_int,
                                       _c_vp, _c_vp]),
+    "bfhip_image_aug_max_taps": (_c_int, []),
+    "bfhip_image_aug_max_cams": (_c_int, []),
+    "bfhip_image_aug_supported": (_c_int, [_c_int] * 8),
+    "bfhip_image_aug": (_c_int, [_c_vp, _c_int, _c_int, _c_vp, _c_vp, ctypes.c_longlong, _c_int, _c_int, _c_vp, _c_int, _c_int,
+                                 _c_vp, _c_vp, ctypes.c_float] + [_c_int] * 4 + [_c_vp, _c_vp]),
 }
 
 

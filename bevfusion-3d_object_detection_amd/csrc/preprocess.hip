@@ -19,14 +19,12 @@
 // blockIdx.y is the (sample, view) image, so the sample's descriptor (passed by value in the kernel arguments: no device
 // table, no copy) is read with a block-uniform index; blockIdx.x walks the image's Hp * ceil(Wp / 8) runs.
 #include "common.h"
+#include "img_store.h"
 
 namespace bfhip {
 namespace {
 
-typedef unsigned short bf16_t;
-
 constexpr int kBlock = 256;
-constexpr int kRun = 8;          // pixels per lane
 constexpr int kMaxSamples = 32;  // descriptors per launch (512 bytes of kernel arguments)
 constexpr int kMaxViews = 1024;  // kMaxSamples * views images = gridDim.y
 
@@ -38,68 +36,6 @@ struct Args {
   int swap, normalise;
   int out_vec;              // Wp % kRun == 0 and a 16-byte aligned output: every store is a 16-byte vector
 };
-
-__device__ __forceinline__ unsigned bf16_rne(float f) {  // fp32 -> bf16, round to nearest even; NaN -> 0x7fc0 as torch does
-  const unsigned u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7fc0u;
-  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
-
-// kRun source elements as fp32: one aligned vector access, or the first n element by element (the rest are never used)
-__device__ __forceinline__ void load_run(const uint8_t *p, int n, float *o) {
-  if (n == kRun && ((uintptr_t)p & 7) == 0) {
-    const uint2 v = *(const uint2 *)p;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      o[j] = (float)((v.x >> (8 * j)) & 0xffu);
-      o[4 + j] = (float)((v.y >> (8 * j)) & 0xffu);
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < kRun; ++j) o[j] = j < n ? (float)p[j] : 0.f;
-  }
-}
-__device__ __forceinline__ void load_run(const float *p, int n, float *o) {
-  if (n == kRun && ((uintptr_t)p & 15) == 0) {
-    const float4 a = *(const float4 *)p, b = *(const float4 *)(p + 4);
-    o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w;
-    o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
-  } else {
-#pragma unroll
-    for (int j = 0; j < kRun; ++j) o[j] = j < n ? p[j] : 0.f;
-  }
-}
-
-// N consecutive output elements: 16-byte stores (q is 16-byte aligned), or the first n element by element
-template <int N>
-__device__ __forceinline__ void store_run(float *q, const float *e, bool vec, int n) {
-  if (vec) {
-#pragma unroll
-    for (int k = 0; k < N; k += 4) *(float4 *)(q + k) = make_float4(e[k], e[k + 1], e[k + 2], e[k + 3]);
-  } else {
-#pragma unroll
-    for (int k = 0; k < N; ++k)
-      if (k < n) q[k] = e[k];
-  }
-}
-template <int N>
-__device__ __forceinline__ void store_run(bf16_t *q, const float *e, bool vec, int n) {
-  if (vec) {
-#pragma unroll
-    for (int k = 0; k < N; k += 8) {
-      uint4 v;
-      v.x = bf16_rne(e[k]) | (bf16_rne(e[k + 1]) << 16);
-      v.y = bf16_rne(e[k + 2]) | (bf16_rne(e[k + 3]) << 16);
-      v.z = bf16_rne(e[k + 4]) | (bf16_rne(e[k + 5]) << 16);
-      v.w = bf16_rne(e[k + 6]) | (bf16_rne(e[k + 7]) << 16);
-      *(uint4 *)(q + k) = v;
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < N; ++k)
-      if (k < n) q[k] = (bf16_t)bf16_rne(e[k]);
-  }
-}
 
 // S: source element (uint8_t / float); O: output element (float / bf16_t); PIX: pixel-major [img, Hp, Wp, 3] output
 template <typename S, typename O, bool PIX>

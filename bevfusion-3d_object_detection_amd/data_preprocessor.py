@@ -9,6 +9,10 @@ once and writes the batch once, optionally already in bf16 and pixel-major (`out
 own keywords) -- the form ResNet50.forward would otherwise make with one more pass.  The arithmetic is the reference's,
 (float(x) - mean) / std in fp32 with a true division, so both paths give the same bits.
 
+`inputs["img_aug_plan"]` (image_aug.ImageAug3D(defer=True)): `img` then holds the RAW uint8 frames [N, H, W, 3] per sample and the
+resize / crop / flip / rotate of ImageAug3D runs on the device in front of the same stores (`process_frames`, csrc/image_aug.hip;
+BFHIP_IMG_AUG=0 or a CPU batch: image_aug.torch_image_aug, then the path below).
+
 BFHIP_IMG_PREPROCESS (ships on; measured: DESIGN.md section 6): 0 selects the plain-torch restatement below, which also
 serves whatever the kernel does not take -- CPU tensors, other dtypes, non-contiguous blocks, a one-value mean.
 """
@@ -184,6 +188,27 @@ class Det3DDataPreprocessor(nn.Module):
                       1 if dtype == torch.bfloat16 else 0, int(self.channels_last), store.data_ptr(), _lib.stream_of(store))
         return out
 
+    def process_frames(self, frames, plans):
+        """Deferred ImageAug3D: frames = per sample the raw uint8 [N, H, W, 3] block (a list, or one [B, N, H, W, 3] tensor),
+        plans = per sample the AugPlan of image_aug.ImageAug3D(defer=True) -> the bits of
+        process_imgs([torch_image_aug(f, p) for f, p in zip(frames, plans)]), on the GPU through csrc/image_aug.hip."""
+        from . import image_aug
+        frames = list(frames.unbind(0)) if torch.is_tensor(frames) else list(frames)
+        plans = [plans] if hasattr(plans, "ndim") and plans.ndim == 2 else list(plans)
+        if len(frames) != len(plans) or not frames:
+            raise ValueError("img_aug_plan: %d plans for %d samples" % (len(plans), len(frames)))
+        dims = {getattr(p, "final_dim", None) for p in plans}
+        if len(dims) != 1 or None in dims:
+            raise ValueError("img_aug_plan: every sample needs an AugPlan with one final_dim, got %s" % sorted(map(str, dims)))
+        if (image_aug.ENABLED and (self.mean is None or self.mean.shape[0] == 3)
+                and all(torch.is_tensor(f) and f.dim() == 4 and len(p) == f.shape[0] for f, p in zip(frames, plans))
+                and image_aug.fused_supported(frames, plans)):
+            image_aug.PATHS["kernel"] += 1
+            return image_aug.fused_image_aug(frames, plans, None, self._mean_std if self.mean is not None else None, self.swap,
+                                             self.pad_size_divisor, self.pad_value, self.out_dtype, self.channels_last)
+        image_aug.PATHS["torch"] += 1
+        return self.process_imgs([image_aug.torch_image_aug(f, p) for f, p in zip(frames, plans)])
+
     # ------------------------------------------------------------------ the reference's entry points
     def forward(self, data, training=False):
         if isinstance(data, (list, tuple)):  # test-time augmentation: one batch dict per augmentation
@@ -197,14 +222,18 @@ class Det3DDataPreprocessor(nn.Module):
         if "points" in inputs:
             batch_inputs["points"] = inputs["points"]
         if "img" in inputs:
-            imgs = self._sample_list(inputs["img"])
-            batch = self.process_imgs(imgs)
+            if inputs.get("img_aug_plan") is not None:  # raw frames + ImageAug3D(defer=True)'s plans: augment on the device
+                batch = self.process_frames(inputs["img"], inputs["img_aug_plan"])
+                sizes = [batch.shape[-2:]] * batch.shape[0]  # every sample is final_dim, padded to the divisor
+            else:
+                imgs = self._sample_list(inputs["img"])
+                batch = self.process_imgs(imgs)
+                sizes = [t.shape[-2:] for t in imgs]
             if samples is not None:
                 d = self.pad_size_divisor
                 shape = tuple(int(v) for v in batch.shape[-2:])
-                for sample, t in zip(samples, imgs):
-                    _set_metainfo(sample, dict(batch_input_shape=shape,
-                                               pad_shape=(round_up(t.shape[-2], d), round_up(t.shape[-1], d))))
+                for sample, hw in zip(samples, sizes):
+                    _set_metainfo(sample, dict(batch_input_shape=shape, pad_shape=(round_up(hw[0], d), round_up(hw[1], d))))
             batch_inputs["imgs"] = batch
         return {"inputs": batch_inputs, "data_samples": samples}
 

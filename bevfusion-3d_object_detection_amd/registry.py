@@ -43,6 +43,7 @@ class Registry:
 
 
 MODELS = Registry("models")
+TRANSFORMS = Registry("transforms")  # data pipeline steps (mmdet3d.registry.TRANSFORMS): ImageAug3D
 
 
 def register(target):

@@ -720,6 +720,43 @@ int bfhip_img_preprocess(const bfhip_img_desc *samples_host, int n_samples, int 
                          const float *mean_host, const float *std_host, float pad_value, int Hp, int Wp, int out_dtype,
                          int pixel_major, void *out, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * ImageAug3D on the device (csrc/image_aug.hip): PIL's bicubic antialiased resize, crop (zero outside), mirror and nearest
+ *   rotation of raw uint8 frames, bit for bit, followed by everything bfhip_img_preprocess does.  Two launches per
+ *   bfhip_image_aug_max_cams() cameras: resize + crop + flip into the uint8 intermediate `mid` [n_samples * views, 3, fH, fW],
+ *   then rotate + swap + normalise + pad + cast into `out` (when no camera rotates the second launch is bfhip_img_preprocess).
+ *   cams_host: n_samples * views descriptors in HOST memory.  data: DEVICE pointer of the camera's frame, uint8 [h, w, 3]
+ *     pixel-major; crop: left / top of the fH x fW crop in the resized image (may hang over any edge: zero there); flip: mirror
+ *     left-right after the crop; rotates != 0: gather out[Y, X] = in[(a5 + X a3 + Y a4) >> 16, (a2 + X a0 + Y a1) >> 16], int32,
+ *     zero outside.  The crop's overlap with the resized image is [h_first, h_first + h_count) x [v_first, v_first + v_count)
+ *     in resized coordinates (a count of 0: the whole output is zero); its resampling tables start at int h_off / v_off of the
+ *     tables: per output one entry (lo, n, k_0 .. k_{taps-1}): out = clamp((2^21 + sum_{j < n} px[lo + j] * k_j) >> 22, 0, 255),
+ *     horizontal pass first with a uint8 result in between, int32 accumulators.
+ *   tables_host / tables_dev: the same table_ints int32 values in host and in device memory.  The host copy is validated
+ *     before anything is launched (every entry inside its source, bounds not decreasing, taps <= bfhip_image_aug_max_taps(),
+ *     no 64-column / 16-row tile over more source than the kernel stages): BFHIP_E_INVALID otherwise.
+ *   bfhip_image_aug_supported: 1 when an axis pair with these sizes and tap counts is within those bounds (taps <= 24 and
+ *     source / resized <= 6.25 per axis: every resize >= 0.2 of a source of 39 pixels or more a side).
+ *   swap_rb .. pixel_major, out: as bfhip_img_preprocess with h = fH and w = fW; every element of out and of mid is written
+ *     exactly once.  No allocation, no synchronisation; everything runs on `stream`.
+ * --------------------------------------------------------------------------------------- */
+typedef struct bfhip_image_aug_cam {
+  const void *data;
+  int h, w;
+  int crop[2];
+  int flip, rotates;
+  int a[6];
+  int h_off, h_taps, h_first, h_count;
+  int v_off, v_taps, v_first, v_count;
+} bfhip_image_aug_cam;
+int bfhip_image_aug_max_taps(void);
+int bfhip_image_aug_max_cams(void);
+int bfhip_image_aug_supported(int src_h, int src_w, int new_h, int new_w, int fH, int fW, int h_taps, int v_taps);
+int bfhip_image_aug(const bfhip_image_aug_cam *cams_host, int n_samples, int views, const int32_t *tables_host,
+                    const int32_t *tables_dev, long long table_ints, int fH, int fW, void *mid, int swap_rb, int normalise,
+                    const float *mean_host, const float *std_host, float pad_value, int Hp, int Wp, int out_dtype,
+                    int pixel_major, void *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
