@@ -1,0 +1,307 @@
+// points_aug.hip -- the point half of the LiDAR augmentation chain on the device (gfx950), for a whole batch at once:
+// GlobalRotScaleTrans (rotate, then translate and scale in either order), RandomFlip3D (sign flips), PointsRangeFilter (strict
+// > min / < max on the transformed xyz, order-preserving compaction) and PointShuffle (a keyed bijection of [0, kept)).
+//
+// The arithmetic is the one points_aug.torch_points_aug defines: every product and sum a separate float32 operation
+// (__fmul_rn / __fadd_rn: nothing contracts them), x' = (x r00 + y r10) + z r20, so the kernels and the torch restatement agree
+// bit for bit.  Columns 3 .. C-1 are copied.
+//
+// Three launches per kMaxSamples samples, count -> scan -> ranked write (voxelize.hip 2a-2c):
+//   1. points_count_kernel: one workgroup of kBlock threads per kBlock consecutive rows of one sample.  The rows (C floats,
+//      12-32 B, not 16-byte aligned in general) are one contiguous run of kBlock * C dwords: consecutive lanes load consecutive
+//      dwords into LDS, then thread t takes row t from there.  Transform, test, wave __ballot / __popcll -> one count per block.
+//   2. points_scan_kernel: ONE workgroup scans the block counts of every sample in turn (exclusive, in place) and writes the
+//      sample's kept count.
+//   3. points_write_kernel: the same load, transform and test; rank = block offset + wave offset + lanes below.  Shuffle off: the
+//      block's kept rows are one contiguous run of the output -- compacted in LDS, stored dword by dword.  Shuffle on: row
+//      perm(rank) of the sample, C stores by the owning thread (a scatter by nature).
+// No launch waits on another block of the same launch.  Sample descriptors travel in the kernel arguments.
+//
+// perm(r), n = kept count: a balanced Feistel network of kRounds rounds on 2 * h bits, h = max(1, ceil(bitlength(n - 1) / 2)),
+// walked until the value is below n (cycle walking: the network is a bijection of [0, 4^h) whatever the round function, so the
+// walk follows the cycle of r, which comes back to r < n: it terminates, and the restriction is a bijection of [0, n)).  Round
+// i: (L, R) <- (R, L ^ (mix(R + key_i) & (2^h - 1))), mix the 32-bit finaliser below; at the end value = L << h | R.
+#include "common.h"
+
+namespace bfhip {
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kWaves = kBlock / kWave;
+constexpr int kMaxC = 8;
+constexpr int kMaxSamples = 16;  // descriptors per launch (kernel arguments)
+constexpr int kRounds = BFHIP_POINTS_AUG_ROUNDS;
+constexpr int kScanBlock = 1024;
+
+enum : int { kHasRTS = 1, kScaleFirst = 2, kFlipY = 4, kFlipX = 8, kHasRange = 16, kShuffle = 32 };
+
+struct Sample {
+  const float *src;
+  int n;
+  int block0;     // first block of the sample in the launch
+  int row0;       // first output row of the sample's region
+  int flags;
+  float r[9], t[3], s, range[6];
+  uint32_t key[kRounds];
+};
+struct Args {
+  Sample s[kMaxSamples];
+  int n_samples, C;
+};
+
+__device__ __forceinline__ uint32_t mix32(uint32_t x) {
+  x = ((x >> 16) ^ x) * 0x45d9f3bu;
+  x = ((x >> 16) ^ x) * 0x45d9f3bu;
+  return (x >> 16) ^ x;
+}
+
+__device__ __forceinline__ uint32_t permute(uint32_t r, uint32_t n, const uint32_t *key) {
+  int bits = 32 - __clz((int)(n - 1));  // n >= 1; n = 1: __clz(0) = 32
+  int h = (bits + 1) >> 1;
+  h = h < 1 ? 1 : h;
+  const uint32_t mask = (1u << h) - 1u;
+  uint32_t v = r;
+  do {
+    uint32_t L = v >> h, R = v & mask;
+#pragma unroll
+    for (int i = 0; i < kRounds; ++i) {
+      const uint32_t f = mix32(R + key[i]) & mask;
+      const uint32_t nr = L ^ f;
+      L = R;
+      R = nr;
+    }
+    v = (L << h) | R;
+  } while (v >= n);
+  return v;
+}
+
+__device__ __forceinline__ int sample_of_block(const Args &a, int b) {
+  int s = 0;
+  for (int i = 1; i < a.n_samples; ++i)
+    if (a.s[i].block0 <= b) s = i;  // block0 does not decrease; empty samples share their successor's: the last one wins
+  return s;
+}
+
+// the block's rows into LDS: rows [first, first + rows) of src, C floats each, consecutive lanes consecutive dwords
+__device__ __forceinline__ void stage_rows(const float *__restrict__ src, long long first, int rows, int C, float *tile) {
+  const float *p = src + first * C;
+  const int nd = rows * C;
+  for (int d = threadIdx.x; d < nd; d += kBlock) tile[d] = p[d];
+}
+
+// transformed xyz of one row and whether it is kept
+__device__ __forceinline__ bool transform(const Sample &sp, float &x, float &y, float &z) {
+  const int f = sp.flags;
+  if (f & kHasRTS) {
+    const float nx = __fadd_rn(__fadd_rn(__fmul_rn(x, sp.r[0]), __fmul_rn(y, sp.r[3])), __fmul_rn(z, sp.r[6]));
+    const float ny = __fadd_rn(__fadd_rn(__fmul_rn(x, sp.r[1]), __fmul_rn(y, sp.r[4])), __fmul_rn(z, sp.r[7]));
+    const float nz = __fadd_rn(__fadd_rn(__fmul_rn(x, sp.r[2]), __fmul_rn(y, sp.r[5])), __fmul_rn(z, sp.r[8]));
+    if (f & kScaleFirst) {
+      x = __fadd_rn(__fmul_rn(nx, sp.s), sp.t[0]);
+      y = __fadd_rn(__fmul_rn(ny, sp.s), sp.t[1]);
+      z = __fadd_rn(__fmul_rn(nz, sp.s), sp.t[2]);
+    } else {
+      x = __fmul_rn(__fadd_rn(nx, sp.t[0]), sp.s);
+      y = __fmul_rn(__fadd_rn(ny, sp.t[1]), sp.s);
+      z = __fmul_rn(__fadd_rn(nz, sp.t[2]), sp.s);
+    }
+  }
+  if (f & kFlipY) y = -y;
+  if (f & kFlipX) x = -x;
+  if (f & kHasRange)
+    return x > sp.range[0] && y > sp.range[1] && z > sp.range[2] && x < sp.range[3] && y < sp.range[4] && z < sp.range[5];
+  return true;
+}
+
+__global__ __launch_bounds__(kBlock) void points_count_kernel(Args a, int *__restrict__ block_counts) {
+  __shared__ float tile[kBlock * kMaxC];
+  __shared__ int wsum[kWaves];
+  const int si = sample_of_block(a, blockIdx.x);
+  const Sample &sp = a.s[si];
+  const long long first = (long long)(blockIdx.x - sp.block0) * kBlock;
+  const int rows = sp.n - first < kBlock ? (int)(sp.n - first) : kBlock;
+  stage_rows(sp.src, first, rows, a.C, tile);
+  __syncthreads();
+  const int t = threadIdx.x;
+  bool keep = false;
+  if (t < rows) {
+    float x = tile[t * a.C], y = tile[t * a.C + 1], z = tile[t * a.C + 2];
+    keep = transform(sp, x, y, z);
+  }
+  const unsigned long long bal = __ballot(keep);
+  if ((t & (kWave - 1)) == 0) wsum[t / kWave] = __popcll(bal);
+  __syncthreads();
+  if (t == 0) {
+    int tot = 0;
+    for (int k = 0; k < kWaves; ++k) tot += wsum[k];
+    block_counts[blockIdx.x] = tot;
+  }
+}
+
+// exclusive scan of each sample's block counts, in place; kept[s] = the sample's total
+__global__ __launch_bounds__(kScanBlock) void points_scan_kernel(Args a, int total_blocks, int *__restrict__ block_counts,
+                                                                 int *__restrict__ kept) {
+  __shared__ int wtot[kScanBlock / kWave];
+  __shared__ int carry;
+  const int t = threadIdx.x, lane = t & (kWave - 1), wv = t / kWave;
+  for (int s = 0; s < a.n_samples; ++s) {
+    const int b0 = a.s[s].block0;
+    const int b1 = s + 1 < a.n_samples ? a.s[s + 1].block0 : total_blocks;
+    if (t == 0) carry = 0;
+    __syncthreads();
+    for (int base = b0; base < b1; base += kScanBlock) {
+      const int i = base + t;
+      const int v = i < b1 ? block_counts[i] : 0;
+      int incl = v;
+      for (int o = 1; o < kWave; o <<= 1) {
+        const int up = __shfl_up(incl, o);
+        if (lane >= o) incl += up;
+      }
+      if (lane == kWave - 1) wtot[wv] = incl;
+      __syncthreads();
+      int woff = 0;
+      for (int k = 0; k < wv; ++k) woff += wtot[k];
+      const int c = carry;
+      if (i < b1) block_counts[i] = c + woff + incl - v;
+      __syncthreads();
+      if (t == kScanBlock - 1) carry = c + woff + incl;
+      __syncthreads();
+    }
+    if (t == 0) kept[s] = carry;
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void points_write_kernel(Args a, const int *__restrict__ block_offs,
+                                                              const int *__restrict__ kept, float *__restrict__ out) {
+  __shared__ float tile[kBlock * kMaxC];
+  __shared__ float packed[kBlock * kMaxC];
+  __shared__ int wsum[kWaves];
+  const int si = sample_of_block(a, blockIdx.x);
+  const Sample &sp = a.s[si];
+  const int C = a.C;
+  const long long first = (long long)(blockIdx.x - sp.block0) * kBlock;
+  const int rows = sp.n - first < kBlock ? (int)(sp.n - first) : kBlock;
+  stage_rows(sp.src, first, rows, C, tile);
+  __syncthreads();
+  const int t = threadIdx.x, lane = t & (kWave - 1), wv = t / kWave;
+  bool keep = false;
+  float x = 0.f, y = 0.f, z = 0.f;
+  if (t < rows) {
+    x = tile[t * C], y = tile[t * C + 1], z = tile[t * C + 2];
+    keep = transform(sp, x, y, z);
+  }
+  const unsigned long long bal = __ballot(keep);
+  const int in_wave = __popcll(bal & ((1ull << lane) - 1ull));
+  if (lane == 0) wsum[wv] = __popcll(bal);
+  __syncthreads();
+  int woff = 0, block_kept = 0;
+  for (int k = 0; k < kWaves; ++k) {
+    if (k < wv) woff += wsum[k];
+    block_kept += wsum[k];
+  }
+  const int local = woff + in_wave;          // rank inside the block
+  const int boff = block_offs[blockIdx.x];   // kept rows of the sample before this block
+  if (sp.flags & kShuffle) {                 // block-uniform
+    if (keep) {
+      const uint32_t row = permute((uint32_t)(boff + local), (uint32_t)kept[si], sp.key);
+      float *dst = out + ((size_t)sp.row0 + row) * C;
+      dst[0] = x, dst[1] = y, dst[2] = z;
+      for (int c = 3; c < C; ++c) dst[c] = tile[t * C + c];
+    }
+    return;
+  }
+  if (keep) {
+    float *dst = packed + local * C;
+    dst[0] = x, dst[1] = y, dst[2] = z;
+    for (int c = 3; c < C; ++c) dst[c] = tile[t * C + c];
+  }
+  __syncthreads();
+  float *dst = out + ((size_t)sp.row0 + boff) * C;
+  const int nd = block_kept * C;
+  for (int d = t; d < nd; d += kBlock) dst[d] = packed[d];
+}
+
+long long blocks_of(long long n) { return (n + kBlock - 1) / kBlock; }
+
+}  // namespace
+}  // namespace bfhip
+
+using namespace bfhip;
+
+BFHIP_EXPORT int bfhip_points_aug_block(void) { return kBlock; }
+
+BFHIP_EXPORT size_t bfhip_points_aug_workspace_bytes(long long total_rows, int n_samples) {
+  if (total_rows < 0 || n_samples < 0) return 0;
+  // one int per block; a sample's last block may be partial
+  return align_up((size_t)(blocks_of(total_rows) + n_samples) * sizeof(int), 256);
+}
+
+BFHIP_EXPORT int bfhip_points_aug(const bfhip_points_aug_sample *samples_host, int n_samples, int C, float *out, int32_t *kept,
+                                  void *workspace, size_t workspace_bytes, void *stream) {
+  BFHIP_REQUIRE(samples_host && kept, "points_aug: a required pointer is NULL");
+  BFHIP_REQUIRE(n_samples >= 1, "points_aug: n_samples=%d", n_samples);
+  BFHIP_REQUIRE(C >= 3 && C <= kMaxC, "points_aug: %d columns (3 .. %d)", C, kMaxC);
+  long long total = 0;
+  for (int i = 0; i < n_samples; ++i) {
+    const bfhip_points_aug_sample &s = samples_host[i];
+    BFHIP_REQUIRE(s.n >= 0 && (s.n == 0 || s.points), "points_aug: sample %d: n=%d points=%p", i, s.n, (const void *)s.points);
+    BFHIP_REQUIRE((s.flags & ~63) == 0, "points_aug: sample %d: flags 0x%x", i, s.flags);
+    BFHIP_REQUIRE(((uintptr_t)s.points & 3) == 0, "points_aug: sample %d: points not 4-byte aligned", i);
+    total += s.n;
+  }
+  BFHIP_REQUIRE(total <= 0x7fffffffll, "points_aug: %lld rows in all (below 2^31)", total);
+  BFHIP_REQUIRE(total == 0 || out, "points_aug: out is NULL");
+  BFHIP_REQUIRE(workspace_bytes >= bfhip_points_aug_workspace_bytes(total, n_samples) && (workspace || total == 0),
+                "points_aug: workspace of %zu bytes, %zu needed", workspace_bytes,
+                bfhip_points_aug_workspace_bytes(total, n_samples));
+  int *counts = (int *)workspace;
+  long long row0 = 0;
+  for (int first = 0; first < n_samples; first += kMaxSamples) {
+    const int n = n_samples - first < kMaxSamples ? n_samples - first : kMaxSamples;
+    Args a;
+    a.n_samples = n;
+    a.C = C;
+    long long blocks = 0;
+    for (int i = 0; i < kMaxSamples; ++i) {
+      Sample &d = a.s[i];
+      if (i >= n) {
+        d = a.s[n - 1];
+        d.n = 0;
+        d.block0 = (int)blocks;
+        continue;
+      }
+      const bfhip_points_aug_sample &s = samples_host[first + i];
+      d.src = s.points;
+      d.n = s.n;
+      d.block0 = (int)blocks;
+      d.row0 = (int)row0;
+      d.flags = s.flags;
+      for (int k = 0; k < 9; ++k) d.r[k] = s.rot[k];
+      for (int k = 0; k < 3; ++k) d.t[k] = s.trans[k];
+      d.s = s.scale;
+      for (int k = 0; k < 6; ++k) d.range[k] = s.range[k];
+      for (int k = 0; k < kRounds; ++k) d.key[k] = s.keys[k];
+      blocks += blocks_of(s.n);
+      row0 += s.n;
+    }
+    if (blocks > 0) {
+      hipLaunchKernelGGL(points_count_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, a, counts);
+      const int rc = check_launch("points_aug count");
+      if (rc != BFHIP_OK) return rc;
+    }
+    // always launched: an all-empty chunk still needs its kept counts (zero) written
+    hipLaunchKernelGGL(points_scan_kernel, dim3(1), dim3(kScanBlock), 0, (hipStream_t)stream, a, (int)blocks, counts,
+                       kept + first);
+    int rc = check_launch("points_aug scan");
+    if (rc != BFHIP_OK) return rc;
+    if (blocks > 0) {
+      hipLaunchKernelGGL(points_write_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, a, counts,
+                         kept + first, out);
+      rc = check_launch("points_aug write");
+      if (rc != BFHIP_OK) return rc;
+    }
+    counts += blocks;
+  }
+  return BFHIP_OK;
+}

@@ -13,6 +13,10 @@ own keywords) -- the form ResNet50.forward would otherwise make with one more pa
 resize / crop / flip / rotate of ImageAug3D runs on the device in front of the same stores (`process_frames`, csrc/image_aug.hip;
 BFHIP_IMG_AUG=0 or a CPU batch: image_aug.torch_image_aug, then the path below).
 
+`inputs["points_aug_plan"]` (the point transforms of points_aug.py with defer=True): `points` then holds the loaded points and the
+rotate / scale / translate, flips, range filter and shuffle of the plans run on the device (`process_points`, csrc/points_aug.hip;
+BFHIP_POINTS_AUG=0 or a CPU batch: points_aug.torch_points_aug, same bits).  Without a plan points pass through as they are.
+
 BFHIP_IMG_PREPROCESS (ships on; measured: DESIGN.md section 6): 0 selects the plain-torch restatement below, which also
 serves whatever the kernel does not take -- CPU tensors, other dtypes, non-contiguous blocks, a one-value mean.
 """
@@ -209,6 +213,14 @@ class Det3DDataPreprocessor(nn.Module):
         image_aug.PATHS["torch"] += 1
         return self.process_imgs([image_aug.torch_image_aug(f, p) for f, p in zip(frames, plans)])
 
+    def process_points(self, points, plans):
+        """Deferred GlobalRotScaleTrans / RandomFlip3D / PointsRangeFilter / PointShuffle: points = per sample the loaded
+        [n, C] tensor, plans = per sample the PointsAugPlan the transforms wrote with defer=True -> the list of float32
+        [kept, C] tensors, views of one buffer, the bits of points_aug.torch_points_aug per sample.  On the GPU through
+        csrc/points_aug.hip; the views' shapes need the B kept counts on the host, read with ONE host read per batch."""
+        from . import points_aug
+        return points_aug.process_points(points, plans)
+
     # ------------------------------------------------------------------ the reference's entry points
     def forward(self, data, training=False):
         if isinstance(data, (list, tuple)):  # test-time augmentation: one batch dict per augmentation
@@ -220,7 +232,10 @@ class Det3DDataPreprocessor(nn.Module):
         inputs, samples = data["inputs"], data.get("data_samples")
         batch_inputs = {}
         if "points" in inputs:
-            batch_inputs["points"] = inputs["points"]
+            if inputs.get("points_aug_plan") is not None:  # the deferred point transforms' plans: augment on the device
+                batch_inputs["points"] = self.process_points(inputs["points"], inputs["points_aug_plan"])
+            else:
+                batch_inputs["points"] = inputs["points"]
         if "img" in inputs:
             if inputs.get("img_aug_plan") is not None:  # raw frames + ImageAug3D(defer=True)'s plans: augment on the device
                 batch = self.process_frames(inputs["img"], inputs["img_aug_plan"])

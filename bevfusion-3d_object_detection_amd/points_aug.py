@@ -1,0 +1,556 @@
+"""The LiDAR half of the reference's training pipeline, between loading and Pack3DDetInputs:
+
+    BEVFusionGlobalRotScaleTrans (BF/transforms_3d.py:164-201) or GlobalRotScaleTrans (M3D/datasets/transforms/transforms_3d.py
+    :631-808) -> BEVFusionRandomFlip3D (BF :130-161) -> PointsRangeFilter (M3D :904-956) -> ObjectRangeFilter (:844-901) ->
+    ObjectNameFilter (:959-1001) -> PointShuffle (:811-841)
+
+under the reference's names, keywords and result keys, with the reference's np.random calls in the reference's order and its
+float32 / float64 arithmetic for `pcd_rotation`, `lidar_aug_matrix` and the boxes (a few dozen rows: always on the host).
+`points` is a float32 [n, C] tensor or array (C >= 3), `gt_bboxes_3d` a float32 [M, 7 or 9] tensor or array in LiDAR
+convention with `gt_labels_3d` beside it; each comes back as the kind it came in.
+
+The points' arithmetic is DEFINED here, by `torch_points_aug(points, plan)`, in elementwise float32 operations:
+
+    x' = (x r00 + y r10) + z r20   (r = pcd_rotation = rot_mat_T; y' and z' likewise), every product and sum rounded once
+    then (v + t) * s for R,T,S (the BEVFusion class) or v * s + t for R,S,T (the plain class)
+    sign flips; the strict > min / < max test on the transformed xyz; order-preserving selection; the shuffle
+
+The reference rotates with a matmul (or, without boxes, an einsum), whose bits depend on the BLAS path a shape takes (fused on
+most rows, one ulp off the unfused order on about half of them); one order is fixed here instead and the tests hold it to the
+reference within the rounding bound of a three-term dot product.
+
+Three ways to the points:
+  * `torch_points_aug(points, plan)`: plain torch on any device -- the specification, the fallback and the yardstick;
+  * the transforms with defer=False: what the reference does, through `torch_points_aug` on the host, one step at a time;
+    PointShuffle indexes by `torch.randperm(n)` exactly as the reference does;
+  * defer=True (the four point transforms): the points are left untouched and each transform appends its step to
+    `data["points_aug_plan"]` (PointsAugPlan); Det3DDataPreprocessor.process_points runs the plans of a batch on the device
+    (`fused_points_aug`, csrc/points_aug.hip: count, scan, ranked write -- three launches and one host read of the kept counts).
+    A plan holds at most one rotate / translate / scale group, then flips, then one range filter, then a shuffle, in that order.
+
+The deferred shuffle departs from the reference on purpose: `randperm(n)` needs n, which exists only after the filter ran on
+the device.  PointShuffle(defer=True) draws one 64-bit seed with `torch.randint` from torch's global generator instead and the
+order is `shuffle_permutation(seed, n_kept)`: a keyed Feistel network on the next even power of two with cycle walking, integer
+operations only, the same in torch and in the kernel.
+
+BFHIP_POINTS_AUG (ships on; measured with tools/points_aug_micro.py: DESIGN.md section 6): 0 sends every deferred batch through
+`torch_points_aug`.  CPU tensors, other dtypes and non-contiguous points go that way as well, with the same bits.  PATHS counts
+the deferred batches each way took.
+"""
+import ctypes
+import os
+
+import numpy as np
+import torch
+
+from . import _lib
+from .registry import TRANSFORMS
+
+ENABLED = os.environ.get("BFHIP_POINTS_AUG", "1") != "0"
+PATHS = {"kernel": 0, "torch": 0}  # deferred point batches taken by each path (tests, tools)
+
+ROUNDS = 6  # BFHIP_POINTS_AUG_ROUNDS
+_M32 = 0xFFFFFFFF
+_M64 = 0xFFFFFFFFFFFFFFFF
+_STAGES = {"rts": 1, "flip": 2, "range": 3, "shuffle": 4}
+
+
+class PointsAugPlan:
+    """What the deferred point transforms of ONE sample add up to; small, picklable, left on the host by
+    Det3DDataPreprocessor.cast_data.  rot float32 [3, 3] (rot_mat_T), trans float32 [3], scale float32, order "RTS" / "RST" (None:
+    no such step), flip_horizontal (y) / flip_vertical (x), range float32 [6] or None, shuffle + its 64-bit seed."""
+    __slots__ = ("rot", "trans", "scale", "order", "flip_horizontal", "flip_vertical", "range", "shuffle", "seed", "stage")
+
+    def __init__(self):
+        self.rot = np.eye(3, dtype=np.float32)
+        self.trans = np.zeros(3, np.float32)
+        self.scale = np.float32(1.0)
+        self.order = None
+        self.flip_horizontal = self.flip_vertical = False
+        self.range = None
+        self.shuffle = False
+        self.seed = 0
+        self.stage = 0
+
+    def __getstate__(self):
+        return {k: getattr(self, k) for k in self.__slots__}
+
+    def __setstate__(self, state):
+        for k, v in state.items():
+            setattr(self, k, v)
+
+    def _enter(self, step):
+        if _STAGES[step] <= self.stage:
+            raise ValueError("points_aug_plan: a %s step cannot follow what the plan already holds (one rotate / translate / scale "
+                             "group, then flips, then one range filter, then a shuffle); run this pipeline with defer=False" % step)
+        self.stage = _STAGES[step]
+
+    def set_rts(self, rot, trans, scale, order):
+        if order not in ("RTS", "RST"):
+            raise ValueError("order must be 'RTS' or 'RST', got %r" % (order,))
+        self._enter("rts")
+        self.rot = np.ascontiguousarray(np.asarray(rot, dtype=np.float32).reshape(3, 3))
+        self.trans = np.ascontiguousarray(np.asarray(trans, dtype=np.float32).reshape(3))
+        self.scale = np.float32(scale)
+        self.order = order
+        return self
+
+    def set_flip(self, horizontal, vertical):
+        self._enter("flip")
+        self.flip_horizontal, self.flip_vertical = bool(horizontal), bool(vertical)
+        return self
+
+    def set_range(self, point_cloud_range):
+        self._enter("range")
+        self.range = np.ascontiguousarray(np.asarray(point_cloud_range, dtype=np.float32).reshape(6))
+        return self
+
+    def set_shuffle(self, seed):
+        self._enter("shuffle")
+        self.shuffle, self.seed = True, int(seed) & _M64
+        return self
+
+    def flags(self):
+        """The `flags` of bfhip_points_aug_sample."""
+        return ((1 if self.order is not None else 0) | (2 if self.order == "RST" else 0) | (4 if self.flip_horizontal else 0) |
+                (8 if self.flip_vertical else 0) | (16 if self.range is not None else 0) | (32 if self.shuffle else 0))
+
+
+# ---------------------------------------------------------------------------------------------- the shuffle
+def shuffle_keys(seed):
+    """The ROUNDS 32-bit round keys of a 64-bit seed: the low halves of consecutive splitmix64 outputs."""
+    z, keys = int(seed) & _M64, []
+    for _ in range(ROUNDS):
+        z = (z + 0x9E3779B97F4A7C15) & _M64
+        x = z
+        x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+        x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & _M64
+        x ^= x >> 31
+        keys.append(x & _M32)
+    return keys
+
+
+def _mix32(x):
+    """int64 tensor holding 32-bit values: the kernel's mix32 (products stay below 2^59, so int64 never wraps)."""
+    x = (((x >> 16) ^ x) * 0x45D9F3B) & _M32
+    x = (((x >> 16) ^ x) * 0x45D9F3B) & _M32
+    return (x >> 16) ^ x
+
+
+def shuffle_permutation(seed, n, device=None):
+    """int64 [n]: perm[r] = the output row of the r-th kept point; a bijection of [0, n).  A balanced Feistel network of ROUNDS
+    rounds on 2 h bits, h = max(1, ceil(bitlength(n - 1) / 2)), round i: (L, R) <- (R, L ^ (mix32(R + key_i) & (2^h - 1))),
+    re-applied while the value is >= n.  The network is a bijection of [0, 4^h) whatever the round function, so the walk
+    follows the cycle of r and comes back into [0, n): it terminates, and distinct r end on distinct rows."""
+    return shuffle_permutations([seed], n, device)[0]
+
+
+def shuffle_permutations(seeds, n, device=None):
+    """int64 [len(seeds), n]: shuffle_permutation of every seed at once."""
+    n = int(n)
+    v = torch.arange(n, dtype=torch.int64, device=device).repeat(len(seeds), 1)
+    if n == 0:
+        return v
+    h = max(1, ((n - 1).bit_length() + 1) // 2)
+    mask = (1 << h) - 1
+    keys = torch.tensor([shuffle_keys(s) for s in seeds], dtype=torch.int64, device=device)
+
+    def network(v):
+        L, R = v >> h, v & mask
+        for i in range(ROUNDS):
+            L, R = R, L ^ (_mix32((R + keys[:, i:i + 1]) & _M32) & mask)
+        return (L << h) | R
+
+    out = network(v)
+    while True:
+        bad = out >= n
+        if not bool(bad.any()):
+            return out
+        out = torch.where(bad, network(out), out)
+
+
+# ---------------------------------------------------------------------------------------------- the defined arithmetic
+def _as_points(points):
+    if isinstance(points, np.ndarray):
+        points = torch.from_numpy(np.ascontiguousarray(points))
+    if not torch.is_tensor(points) or points.dim() != 2 or points.shape[1] < 3:
+        raise ValueError("points must be a [n, C] tensor or array with C >= 3")
+    return points if points.dtype == torch.float32 else points.to(torch.float32)
+
+
+def _range_mask(x, y, z, rng):
+    lo0, lo1, lo2, hi0, hi1, hi2 = (float(v) for v in rng)
+    return (x > lo0) & (y > lo1) & (z > lo2) & (x < hi0) & (y < hi1) & (z < hi2)
+
+
+def transformed_xyz(points, plan):
+    """(x, y, z) float32 [n] each: the plan's rotate / translate / scale and flips of points[:, :3]."""
+    x, y, z = points[:, 0], points[:, 1], points[:, 2]
+    if plan.order is not None:
+        r = [[float(v) for v in row] for row in plan.rot]
+        t = [float(v) for v in plan.trans]
+        s = float(plan.scale)
+        x, y, z = ((x * r[0][0] + y * r[1][0]) + z * r[2][0],
+                   (x * r[0][1] + y * r[1][1]) + z * r[2][1],
+                   (x * r[0][2] + y * r[1][2]) + z * r[2][2])
+        if plan.order == "RTS":
+            x, y, z = (x + t[0]) * s, (y + t[1]) * s, (z + t[2]) * s
+        else:
+            x, y, z = x * s + t[0], y * s + t[1], z * s + t[2]
+    if plan.flip_horizontal:
+        y = -y
+    if plan.flip_vertical:
+        x = -x
+    return x, y, z
+
+
+def torch_points_aug(points, plan, return_mask=False):
+    """points [n, C] (tensor on any device, or array) + PointsAugPlan -> float32 [kept, C] on the points' device: the
+    specification csrc/points_aug.hip restates bit for bit.  return_mask: also the bool [n] of the rows the filter kept."""
+    p = _as_points(points)
+    x, y, z = transformed_xyz(p, plan)
+    out = torch.cat([torch.stack([x, y, z], 1), p[:, 3:]], 1)
+    mask = None
+    if plan.range is not None:
+        mask = _range_mask(x, y, z, plan.range)
+        out = out[mask]
+    elif return_mask:
+        mask = torch.ones(p.shape[0], dtype=torch.bool, device=p.device)
+    if plan.shuffle:
+        perm = shuffle_permutation(plan.seed, out.shape[0], out.device)
+        dst = torch.empty_like(out)
+        dst[perm] = out
+        out = dst
+    return (out, mask) if return_mask else out
+
+
+# ---------------------------------------------------------------------------------------------- the device path
+class _Sample(ctypes.Structure):
+    """bfhip_points_aug_sample (include/bevfusion_hip.h)."""
+    _fields_ = [("points", ctypes.c_void_p), ("n", ctypes.c_int), ("flags", ctypes.c_int), ("rot", ctypes.c_float * 9),
+                ("trans", ctypes.c_float * 3), ("scale", ctypes.c_float), ("range", ctypes.c_float * 6),
+                ("keys", ctypes.c_uint32 * ROUNDS)]
+
+
+def fused_supported(points):
+    """True when bfhip_points_aug takes this batch: float32 contiguous [n, C] device tensors on one device, one C in 3 .. 8,
+    fewer than 2^31 rows in all."""
+    if not points or not all(torch.is_tensor(p) and p.is_cuda and p.dtype == torch.float32 and p.dim() == 2
+                             and p.is_contiguous() and p.device == points[0].device and p.shape[1] == points[0].shape[1]
+                             for p in points):
+        return False
+    return 3 <= points[0].shape[1] <= 8 and sum(int(p.shape[0]) for p in points) < (1 << 31)
+
+
+def descriptors(points, plans):
+    """The bfhip_points_aug_sample array of a batch."""
+    descs = (_Sample * len(points))()
+    for d, p, plan in zip(descs, points, plans):
+        d.points, d.n, d.flags = (p.data_ptr() if p.shape[0] else None), int(p.shape[0]), plan.flags()
+        d.rot[:] = [float(v) for v in plan.rot.reshape(-1)]
+        d.trans[:] = [float(v) for v in plan.trans]
+        d.scale = float(plan.scale)
+        d.range[:] = [float(v) for v in plan.range] if plan.range is not None else [0.0] * 6
+        d.keys[:] = shuffle_keys(plan.seed) if plan.shuffle else [0] * ROUNDS
+    return descs
+
+
+def fused_points_aug(points, plans):
+    """points: list of device float32 [n_i, C]; plans: list of PointsAugPlan -> the list of [kept_i, C] tensors, views of one
+    buffer of sum(n_i) rows.  Three launches per 16 samples, then ONE host read per batch: the B kept counts, which the views'
+    shapes need (it waits for the launches)."""
+    B, C, dev = len(points), int(points[0].shape[1]), points[0].device
+    sizes = [int(p.shape[0]) for p in points]
+    total = sum(sizes)
+    out = torch.empty((total, C), dtype=torch.float32, device=dev)
+    kept = torch.empty(B, dtype=torch.int32, device=dev)
+    nbytes = _lib.call_size("bfhip_points_aug_workspace_bytes", total, B)
+    work = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    descs = descriptors(points, plans)
+    with torch.cuda.device(dev):
+        _lib.call("bfhip_points_aug", descs, B, C, out.data_ptr() if total else None, kept.data_ptr(), work.data_ptr(), nbytes,
+                  _lib.stream_of(out))
+    counts = kept.cpu().tolist()  # the batch's one host read
+    views, row = [], 0
+    for n, k in zip(sizes, counts):
+        views.append(out[row:row + k])
+        row += n
+    return views
+
+
+def process_points(points, plans):
+    """Deferred point transforms of a batch: points = per sample [n_i, C], plans = per sample the PointsAugPlan -> the list of
+    float32 [kept_i, C] tensors (views of one buffer), the bits of [torch_points_aug(p, plan) ...].  On the GPU through
+    csrc/points_aug.hip, which costs one host read per batch (the kept counts)."""
+    points = list(points)
+    plans = [plans] if isinstance(plans, PointsAugPlan) else list(plans)
+    if len(points) != len(plans) or not points:
+        raise ValueError("points_aug_plan: %d plans for %d samples" % (len(plans), len(points)))
+    if not all(isinstance(p, PointsAugPlan) for p in plans):
+        raise TypeError("points_aug_plan: every sample needs a PointsAugPlan")
+    if ENABLED and fused_supported(points):
+        PATHS["kernel"] += 1
+        return fused_points_aug(points, plans)
+    PATHS["torch"] += 1
+    outs = [torch_points_aug(p, plan) for p, plan in zip(points, plans)]
+    if len({o.shape[1] for o in outs}) != 1 or len({o.device for o in outs}) != 1:
+        return outs
+    return list(torch.cat(outs, 0).split([int(o.shape[0]) for o in outs], 0))
+
+
+# ---------------------------------------------------------------------------------------------- the transforms
+def _unwrap(value):
+    """(float32 tensor that may be edited in place, was it an array)."""
+    if isinstance(value, np.ndarray):
+        return torch.from_numpy(np.array(value, dtype=np.float32)), True
+    return torch.as_tensor(value).to(torch.float32).clone(), False
+
+
+def _wrap(tensor, was_array):
+    return tensor.numpy() if was_array else tensor
+
+
+def _plan_of(data):
+    for key in ("pts_instance_mask", "pts_semantic_mask"):
+        if data.get(key) is not None:
+            raise ValueError("defer=True does not carry %s through the filter and the shuffle; use defer=False" % key)
+    plan = data.get("points_aug_plan")
+    if plan is None:
+        plan = data["points_aug_plan"] = PointsAugPlan()
+    return plan
+
+
+def _apply(data, plan):
+    """One eager step on data["points"]; the filter's mask, if any."""
+    pts = data["points"]
+    out, mask = torch_points_aug(pts, plan, return_mask=True)
+    data["points"] = out.numpy() if isinstance(pts, np.ndarray) else out
+    return mask
+
+
+def rotation_matrix(angle):
+    """(rot_mat_T float32 [3, 3], the float32 angle): rotation_3d_in_axis(..., axis=2, return_mat=True) of one angle, operation
+    for operation (M3D/structures/bbox_3d/utils.py:64-121)."""
+    angle = torch.tensor(angle, dtype=torch.float32)
+    angles = torch.full((1,), angle)
+    rot_sin, rot_cos = torch.sin(angles), torch.cos(angles)
+    ones, zeros = torch.ones_like(rot_cos), torch.zeros_like(rot_cos)
+    rot = torch.stack([torch.stack([rot_cos, rot_sin, zeros]), torch.stack([-rot_sin, rot_cos, zeros]),
+                       torch.stack([zeros, zeros, ones])])
+    return torch.einsum("jka->ajk", rot).squeeze(0), angle
+
+
+@TRANSFORMS.register_module()
+class GlobalRotScaleTrans:
+    """The reference's GlobalRotScaleTrans: rotate about z, scale, translate (`transformation_3d_flow` gets R, S, T).  Writes
+    pcd_rotation (float32 tensor [3, 3], rot_mat_T), pcd_rotation_angle, pcd_scale_factor, pcd_trans."""
+    ORDER = "RST"
+
+    def __init__(self, rot_range=(-0.78539816, 0.78539816), scale_ratio_range=(0.95, 1.05), translation_std=(0, 0, 0),
+                 shift_height=False, defer=False):
+        seq = (list, tuple, np.ndarray)
+        if not isinstance(rot_range, seq):
+            rot_range = [-rot_range, rot_range]
+        if not isinstance(scale_ratio_range, seq):
+            raise TypeError("unsupported scale_ratio_range type %s" % type(scale_ratio_range))
+        if not isinstance(translation_std, seq):
+            translation_std = [translation_std] * 3
+        if not all(std >= 0 for std in translation_std):
+            raise ValueError("translation_std should be positive")
+        if defer and shift_height:
+            raise ValueError("defer=True does not scale a height column (shift_height=True); use defer=False")
+        self.rot_range, self.scale_ratio_range, self.translation_std = rot_range, scale_ratio_range, translation_std
+        self.shift_height, self.defer = bool(shift_height), bool(defer)
+
+    def transform(self, data):
+        if "transformation_3d_flow" not in data:
+            data["transformation_3d_flow"] = []
+        noise_rotation = np.random.uniform(self.rot_range[0], self.rot_range[1])
+        if "pcd_scale_factor" not in data:
+            data["pcd_scale_factor"] = np.random.uniform(self.scale_ratio_range[0], self.scale_ratio_range[1])
+        trans = np.random.normal(scale=np.array(self.translation_std, dtype=np.float32), size=3).T
+        scale = data["pcd_scale_factor"]
+        rot, angle = rotation_matrix(noise_rotation)
+        data["pcd_rotation"], data["pcd_rotation_angle"], data["pcd_trans"] = rot, noise_rotation, trans
+
+        if "gt_bboxes_3d" in data:
+            b, was_array = _unwrap(data["gt_bboxes_3d"])
+            if len(b):  # LiDARInstance3DBoxes.rotate
+                b[:, 0:3] = torch.einsum("aij,jka->aik", b[:, 0:3][None], rot[:, :, None]).squeeze(0)
+                b[:, 6] += angle
+                if b.shape[1] == 9:
+                    b[:, 7:9] = b[:, 7:9] @ rot[:2, :2]
+            steps = {"T": lambda: b[:, :3].add_(b.new_tensor(trans)),
+                     "S": lambda: (b[:, :6].mul_(scale), b[:, 7:].mul_(scale)) if len(b) else None}
+            for step in self.ORDER[1:]:
+                steps[step]()
+            data["gt_bboxes_3d"] = _wrap(b, was_array)
+
+        if self.defer:
+            _plan_of(data).set_rts(rot.numpy(), trans, scale, self.ORDER)
+        else:
+            _apply(data, PointsAugPlan().set_rts(rot.numpy(), trans, scale, self.ORDER))
+            if self.shift_height:  # the reference scales the height attribute too; its column is the caller's to name
+                col = data.get("points_height_dim")
+                if col is None:
+                    raise ValueError("shift_height=True needs data['points_height_dim'], the column of the height attribute")
+                pts = data["points"]
+                pts[:, col] = pts[:, col] * np.float32(scale)
+        data["transformation_3d_flow"].extend(list(self.ORDER))
+        return data
+
+    __call__ = transform
+
+
+@TRANSFORMS.register_module()
+class BEVFusionGlobalRotScaleTrans(GlobalRotScaleTrans):
+    """The BEVFusion configs' variant: rotate, translate, scale (R, T, S), and the 4 x 4 float64 `lidar_aug_matrix` the view
+    transform consumes."""
+    ORDER = "RTS"
+
+    def transform(self, data):
+        data = super().transform(data)
+        lidar_augs = np.eye(4)
+        lidar_augs[:3, :3] = (data["pcd_rotation"].T * data["pcd_scale_factor"]).numpy()
+        lidar_augs[:3, 3] = data["pcd_trans"] * data["pcd_scale_factor"]
+        if "lidar_aug_matrix" not in data:
+            data["lidar_aug_matrix"] = np.eye(4)
+        data["lidar_aug_matrix"] = lidar_augs @ data["lidar_aug_matrix"]
+        return data
+
+    __call__ = transform
+
+
+@TRANSFORMS.register_module()
+class BEVFusionRandomFlip3D:
+    """Two coin flips: horizontal negates y, vertical negates x, of the points, the boxes (with their yaw and velocity) and the
+    BEV masks; both compose into `lidar_aug_matrix`.  The two draws are also recorded as `pcd_horizontal_flip` /
+    `pcd_vertical_flip` (RandomFlip3D's keys; the reference's BEVFusion class keeps them to itself)."""
+
+    def __init__(self, defer=False):
+        self.defer = bool(defer)
+
+    def transform(self, data):
+        flip_horizontal = np.random.choice([0, 1])
+        flip_vertical = np.random.choice([0, 1])
+        rotation = np.eye(3)
+        b = None
+        if "gt_bboxes_3d" in data:
+            b, was_array = _unwrap(data["gt_bboxes_3d"])
+        if flip_horizontal:
+            rotation = np.array([[1, 0, 0], [0, -1, 0], [0, 0, 1]]) @ rotation
+            if b is not None:
+                b[:, 1::7] = -b[:, 1::7]
+                b[:, 6] = -b[:, 6]
+            if "gt_masks_bev" in data:
+                data["gt_masks_bev"] = data["gt_masks_bev"][:, :, ::-1].copy()
+        if flip_vertical:
+            rotation = np.array([[-1, 0, 0], [0, 1, 0], [0, 0, 1]]) @ rotation
+            if b is not None:
+                b[:, 0::7] = -b[:, 0::7]
+                b[:, 6] = -b[:, 6] + np.pi
+            if "gt_masks_bev" in data:
+                data["gt_masks_bev"] = data["gt_masks_bev"][:, ::-1, :].copy()
+        if b is not None:
+            data["gt_bboxes_3d"] = _wrap(b, was_array)
+        if "points" in data:
+            if self.defer:
+                _plan_of(data).set_flip(flip_horizontal, flip_vertical)
+            else:
+                _apply(data, PointsAugPlan().set_flip(flip_horizontal, flip_vertical))
+        if "lidar_aug_matrix" not in data:
+            data["lidar_aug_matrix"] = np.eye(4)
+        data["lidar_aug_matrix"][:3, :] = rotation @ data["lidar_aug_matrix"][:3, :]
+        data["pcd_horizontal_flip"], data["pcd_vertical_flip"] = bool(flip_horizontal), bool(flip_vertical)
+        return data
+
+    __call__ = transform
+
+
+@TRANSFORMS.register_module()
+class PointsRangeFilter:
+    """Keeps the points strictly inside point_cloud_range (x, y, z minimum, then maximum), in their order."""
+
+    def __init__(self, point_cloud_range, defer=False):
+        self.pcd_range = np.array(point_cloud_range, dtype=np.float32)
+        self.defer = bool(defer)
+
+    def transform(self, data):
+        if self.defer:
+            _plan_of(data).set_range(self.pcd_range)
+            return data
+        mask = _apply(data, PointsAugPlan().set_range(self.pcd_range)).numpy()
+        for key in ("pts_instance_mask", "pts_semantic_mask"):
+            if data.get(key) is not None:
+                data[key] = data[key][mask]
+        return data
+
+    __call__ = transform
+
+
+@TRANSFORMS.register_module()
+class ObjectRangeFilter:
+    """Keeps the boxes whose centre lies strictly inside the BEV range and wraps their yaw into [-pi, pi)."""
+
+    def __init__(self, point_cloud_range):
+        self.pcd_range = np.array(point_cloud_range, dtype=np.float32)
+
+    def transform(self, data):
+        b, was_array = _unwrap(data["gt_bboxes_3d"])
+        r = self.pcd_range[[0, 1, 3, 4]]
+        mask = (b[:, 0] > r[0]) & (b[:, 1] > r[1]) & (b[:, 0] < r[2]) & (b[:, 1] < r[3])
+        b = b[mask]
+        labels = data["gt_labels_3d"]
+        data["gt_labels_3d"] = labels[mask] if torch.is_tensor(labels) else np.asarray(labels)[mask.numpy().astype(bool)]
+        period = 2 * np.pi  # limit_yaw(offset=0.5, period=2 pi)
+        b[:, 6] = b[:, 6] - torch.floor(b[:, 6] / period + 0.5) * period
+        data["gt_bboxes_3d"] = _wrap(b, was_array)
+        return data
+
+    __call__ = transform
+
+
+@TRANSFORMS.register_module()
+class ObjectNameFilter:
+    """Keeps the boxes whose label is one of range(len(classes))."""
+
+    def __init__(self, classes):
+        self.classes = classes
+        self.labels = list(range(len(self.classes)))
+
+    def transform(self, data):
+        labels = data["gt_labels_3d"]
+        keep = np.array([int(n) in self.labels for n in labels], dtype=bool)
+        boxes = data["gt_bboxes_3d"]
+        if torch.is_tensor(boxes):
+            data["gt_bboxes_3d"] = boxes[torch.from_numpy(keep)]
+        else:
+            data["gt_bboxes_3d"] = np.asarray(boxes)[keep]
+        data["gt_labels_3d"] = labels[torch.from_numpy(keep)] if torch.is_tensor(labels) else np.asarray(labels)[keep]
+        return data
+
+    __call__ = transform
+
+
+@TRANSFORMS.register_module()
+class PointShuffle:
+    """defer=False: points[torch.randperm(n)], as the reference.  defer=True: one torch.randint for the plan's 64-bit seed; the
+    order is shuffle_permutation(seed, number of points the filter kept)."""
+
+    def __init__(self, defer=False):
+        self.defer = bool(defer)
+
+    def transform(self, data):
+        if self.defer:
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+            _plan_of(data).set_shuffle(seed)
+            return data
+        pts = data["points"]
+        idx = torch.randperm(len(pts))
+        data["points"] = pts[idx.numpy()] if isinstance(pts, np.ndarray) else pts[idx]
+        for key in ("pts_instance_mask", "pts_semantic_mask"):
+            if data.get(key) is not None:
+                data[key] = data[key][idx.numpy()]
+        return data
+
+    __call__ = transform

@@ -43,7 +43,10 @@ class Registry:
 
 
 MODELS = Registry("models")
-TRANSFORMS = Registry("transforms")  # data pipeline steps (mmdet3d.registry.TRANSFORMS): ImageAug3D
+# data pipeline steps (mmdet3d.registry.TRANSFORMS): ImageAug3D (image_aug.py) and the LiDAR chain (points_aug.py):
+# BEVFusionGlobalRotScaleTrans, GlobalRotScaleTrans, BEVFusionRandomFlip3D, PointsRangeFilter, ObjectRangeFilter,
+# ObjectNameFilter, PointShuffle
+TRANSFORMS = Registry("transforms")
 
 
 def register(target):

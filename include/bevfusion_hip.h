@@ -757,6 +757,40 @@ int bfhip_image_aug(const bfhip_image_aug_cam *cams_host, int n_samples, int vie
                     const float *mean_host, const float *std_host, float pad_value, int Hp, int Wp, int out_dtype,
                     int pixel_major, void *out, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * The point half of the LiDAR augmentation chain on the device (csrc/points_aug.hip): GlobalRotScaleTrans /
+ *   BEVFusionGlobalRotScaleTrans, BEVFusionRandomFlip3D, PointsRangeFilter and PointShuffle
+ *   (M3D/datasets/transforms/transforms_3d.py:631-956, BF/transforms_3d.py:130-201) of a whole batch in three launches per 16
+ *   samples: count per block, one-block scan, ranked write.
+ *   samples_host: n_samples descriptors in HOST memory.  points: DEVICE float32 [n, C], 4-byte aligned, 3 <= C <= 8.
+ *     flags: 1 rotate + translate + scale present; 2 scale before translate (R,S,T; otherwise R,T,S); 4 negate y (horizontal
+ *     flip); 8 negate x (vertical flip); 16 range filter present; 32 shuffle.  rot: rot_mat_T row-major,
+ *     x' = (x rot[0] + y rot[3]) + z rot[6], y' with rot[1], rot[4], rot[7], z' with rot[2], rot[5], rot[8]; then (v + trans) *
+ *     scale, or v * scale + trans; every product and sum one float32 operation, never fused.  range: (x, y, z) minimum and
+ *     maximum, a row is kept when every transformed coordinate is strictly inside.  keys: the round keys of the shuffle, a
+ *     balanced Feistel network of BFHIP_POINTS_AUG_ROUNDS rounds on the next even power of two with cycle walking
+ *     (bevfusion_amd/points_aug.py: shuffle_permutation is its definition).
+ *   out: float32 [sum n, C]; sample i owns the rows from sum_{j < i} n_j on and its first kept[i] rows are written: the kept
+ *     rows in input order, or, with the shuffle, the r-th kept row at row perm(r).  Columns 3 .. C-1 are copied.
+ *   kept: int32 [n_samples], written for every sample (0 for an empty one).  sum n < 2^31.
+ *   No allocation, no synchronisation; everything runs on `stream`.  bfhip_points_aug_block: rows per workgroup.
+ * --------------------------------------------------------------------------------------- */
+#define BFHIP_POINTS_AUG_ROUNDS 6
+typedef struct bfhip_points_aug_sample {
+  const float *points;
+  int n;
+  int flags;
+  float rot[9];
+  float trans[3];
+  float scale;
+  float range[6];
+  uint32_t keys[BFHIP_POINTS_AUG_ROUNDS];
+} bfhip_points_aug_sample;
+int bfhip_points_aug_block(void);
+size_t bfhip_points_aug_workspace_bytes(long long total_rows, int n_samples);
+int bfhip_points_aug(const bfhip_points_aug_sample *samples_host, int n_samples, int C, float *out, int32_t *kept,
+                     void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
