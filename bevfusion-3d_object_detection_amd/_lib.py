@@ -156,6 +156,8 @@ SIGNATURES = {
     "bfhip_points_aug_block": (_c_int, []),
     "bfhip_points_aug_workspace_bytes": (_c_sz, [ctypes.c_longlong, _c_int]),
     "bfhip_points_aug": (_c_int, [_c_vp, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_sz, _c_vp]),
+    "bfhip_points_aug_max_boxes": (_c_int, []),
+    "bfhip_points_aug_paste": (_c_int, [_c_vp, _c_vp, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_sz, _c_vp]),
 }
 
 

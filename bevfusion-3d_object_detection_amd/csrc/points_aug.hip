@@ -17,6 +17,16 @@
 //      perm(rank) of the sample, C stores by the owning thread (a scatter by nature).
 // No launch waits on another block of the same launch.  Sample descriptors travel in the kernel arguments.
 //
+// ObjectSample's paste (bfhip_points_aug_paste) is a compile-time variant of kernels 1 and 3, HasPaste; the instantiation
+// without it is what bfhip_points_aug launches, as before.  With it a sample's row space is [m pasted rows ; n original rows]:
+// the pasted rows and the sample's K x 6 plane equations (K <= kMaxBoxes) live in device memory, their pointers and counts
+// travel beside the sample descriptors (Args + PasteArgs: 2.4 KB of the 4 KB of kernel arguments), stage_rows_paste fills
+// the tile from both sources when a block straddles the boundary and puts the plane table into LDS (6 KB at the cap) once
+// per block.  An original row is kept when it is inside no box -- for some plane ((x n0 + y n1) + z n2) + d >= 0, on the
+// UNtransformed xyz, unfused like the rotation; all lanes of a wave read the same plane (an LDS broadcast) and leave a box at its
+// first such plane -- and then passes the chain above; pasted rows skip the box test.  Scan, ranks and shuffle do not change:
+// they see one sample of m + n rows.
+//
 // perm(r), n = kept count: a balanced Feistel network of kRounds rounds on 2 * h bits, h = max(1, ceil(bitlength(n - 1) / 2)),
 // walked until the value is below n (cycle walking: the network is a bijection of [0, 4^h) whatever the round function, so the
 // walk follows the cycle of r, which comes back to r < n: it terminates, and the restriction is a bijection of [0, n)).  Round
@@ -32,6 +42,7 @@ constexpr int kMaxC = 8;
 constexpr int kMaxSamples = 16;  // descriptors per launch (kernel arguments)
 constexpr int kRounds = BFHIP_POINTS_AUG_ROUNDS;
 constexpr int kScanBlock = 1024;
+constexpr int kMaxBoxes = 64;    // pasted boxes per sample: the plane table is kMaxBoxes * 24 floats of LDS (6 KB)
 
 enum : int { kHasRTS = 1, kScaleFirst = 2, kFlipY = 4, kFlipX = 8, kHasRange = 16, kShuffle = 32 };
 
@@ -48,6 +59,16 @@ struct Args {
   Sample s[kMaxSamples];
   int n_samples, C;
 };
+// the paste of one sample: m rows in front of the sample's own, K boxes as K x 6 plane equations (both in device memory)
+struct Paste {
+  const float *pts;
+  const float *planes;
+  int m, K;
+};
+struct PasteArgs {
+  Paste p[kMaxSamples];
+};
+static_assert(sizeof(Args) + sizeof(PasteArgs) + 3 * sizeof(void *) <= 4096, "kernel arguments: HIP passes at most 4 KB");
 
 __device__ __forceinline__ uint32_t mix32(uint32_t x) {
   x = ((x >> 16) ^ x) * 0x45d9f3bu;
@@ -113,20 +134,64 @@ __device__ __forceinline__ bool transform(const Sample &sp, float &x, float &y, 
   return true;
 }
 
-__global__ __launch_bounds__(kBlock) void points_count_kernel(Args a, int *__restrict__ block_counts) {
+// stage_rows for a block of a sample with a paste: rows [first, first + rows) of the row space [m pasted rows ; original
+// rows] (the boundary generally falls inside the block's run of dwords), and the sample's plane table
+__device__ __forceinline__ void stage_rows_paste(const Paste &pd, const float *__restrict__ src, long long first, int rows, int C,
+                                                 float *tile, float *planes) {
+  const int nd = rows * C;
+  const long long b = ((long long)pd.m - first) * C;  // dwords of the run that come from the pasted rows
+  const int bd = b < 0 ? 0 : (b > nd ? nd : (int)b);
+  const long long p0 = first * C, s0 = (first - pd.m) * C;  // s0 + d >= 0 wherever d >= bd
+  for (int d = threadIdx.x; d < nd; d += kBlock) tile[d] = d < bd ? pd.pts[p0 + d] : src[s0 + d];
+  const int np = pd.K * 24;
+  for (int d = threadIdx.x; d < np; d += kBlock) planes[d] = pd.planes[d];
+}
+
+// is the untransformed (x, y, z) inside any of the K boxes?  planes: K x 6 x (n0, n1, n2, d) in LDS; every lane of a wave reads
+// the same plane at the same time (a broadcast), and a box is left at its first plane with sign >= 0
+__device__ __forceinline__ bool inside_any_box(const float *planes, int K, float x, float y, float z) {
+  for (int j = 0; j < K; ++j) {
+    const float *pl = planes + j * 24;
+    bool inside = true;
+    for (int k = 0; k < 6; ++k) {
+      const float sign = __fadd_rn(
+          __fadd_rn(__fadd_rn(__fmul_rn(x, pl[4 * k]), __fmul_rn(y, pl[4 * k + 1])), __fmul_rn(z, pl[4 * k + 2])), pl[4 * k + 3]);
+      if (!(sign < 0.f)) {
+        inside = false;
+        break;
+      }
+    }
+    if (inside) return true;
+  }
+  return false;
+}
+
+// One block of the count kernel.  HasPaste: the sample's row space is its m pasted rows, then its n original rows (sp.n = m +
+// n), the block's run of rows may straddle the boundary, the plane table goes to LDS once per block and an original row inside
+// any box is not kept.
+template <bool HasPaste>
+__device__ __forceinline__ void count_block(const Args &a, const PasteArgs *pa, int *__restrict__ block_counts) {
   __shared__ float tile[kBlock * kMaxC];
   __shared__ int wsum[kWaves];
+  __shared__ float planes[HasPaste ? kMaxBoxes * 24 : 1];  // without a paste: unused, and gone from the kernel
   const int si = sample_of_block(a, blockIdx.x);
   const Sample &sp = a.s[si];
   const long long first = (long long)(blockIdx.x - sp.block0) * kBlock;
   const int rows = sp.n - first < kBlock ? (int)(sp.n - first) : kBlock;
-  stage_rows(sp.src, first, rows, a.C, tile);
+  if constexpr (HasPaste) {
+    stage_rows_paste(pa->p[si], sp.src, first, rows, a.C, tile, planes);
+  } else {
+    stage_rows(sp.src, first, rows, a.C, tile);
+  }
   __syncthreads();
   const int t = threadIdx.x;
   bool keep = false;
   if (t < rows) {
     float x = tile[t * a.C], y = tile[t * a.C + 1], z = tile[t * a.C + 2];
+    bool dropped = false;
+    if constexpr (HasPaste) dropped = first + t >= pa->p[si].m && inside_any_box(planes, pa->p[si].K, x, y, z);
     keep = transform(sp, x, y, z);
+    if constexpr (HasPaste) keep = keep && !dropped;
   }
   const unsigned long long bal = __ballot(keep);
   if ((t & (kWave - 1)) == 0) wsum[t / kWave] = __popcll(bal);
@@ -136,6 +201,14 @@ __global__ __launch_bounds__(kBlock) void points_count_kernel(Args a, int *__res
     for (int k = 0; k < kWaves; ++k) tot += wsum[k];
     block_counts[blockIdx.x] = tot;
   }
+}
+
+__global__ __launch_bounds__(kBlock) void points_count_kernel(Args a, int *__restrict__ block_counts) {
+  count_block<false>(a, nullptr, block_counts);
+}
+
+__global__ __launch_bounds__(kBlock) void points_count_paste_kernel(Args a, PasteArgs pa, int *__restrict__ block_counts) {
+  count_block<true>(a, &pa, block_counts);
 }
 
 // exclusive scan of each sample's block counts, in place; kept[s] = the sample's total
@@ -172,24 +245,33 @@ __global__ __launch_bounds__(kScanBlock) void points_scan_kernel(Args a, int tot
   }
 }
 
-__global__ __launch_bounds__(kBlock) void points_write_kernel(Args a, const int *__restrict__ block_offs,
-                                                              const int *__restrict__ kept, float *__restrict__ out) {
+template <bool HasPaste>
+__device__ __forceinline__ void write_block(const Args &a, const PasteArgs *pa, const int *__restrict__ block_offs,
+                                            const int *__restrict__ kept, float *__restrict__ out) {
   __shared__ float tile[kBlock * kMaxC];
   __shared__ float packed[kBlock * kMaxC];
   __shared__ int wsum[kWaves];
+  __shared__ float planes[HasPaste ? kMaxBoxes * 24 : 1];
   const int si = sample_of_block(a, blockIdx.x);
   const Sample &sp = a.s[si];
   const int C = a.C;
   const long long first = (long long)(blockIdx.x - sp.block0) * kBlock;
   const int rows = sp.n - first < kBlock ? (int)(sp.n - first) : kBlock;
-  stage_rows(sp.src, first, rows, C, tile);
+  if constexpr (HasPaste) {
+    stage_rows_paste(pa->p[si], sp.src, first, rows, C, tile, planes);
+  } else {
+    stage_rows(sp.src, first, rows, C, tile);
+  }
   __syncthreads();
   const int t = threadIdx.x, lane = t & (kWave - 1), wv = t / kWave;
   bool keep = false;
   float x = 0.f, y = 0.f, z = 0.f;
   if (t < rows) {
     x = tile[t * C], y = tile[t * C + 1], z = tile[t * C + 2];
+    bool dropped = false;
+    if constexpr (HasPaste) dropped = first + t >= pa->p[si].m && inside_any_box(planes, pa->p[si].K, x, y, z);
     keep = transform(sp, x, y, z);
+    if constexpr (HasPaste) keep = keep && !dropped;
   }
   const unsigned long long bal = __ballot(keep);
   const int in_wave = __popcll(bal & ((1ull << lane) - 1ull));
@@ -220,6 +302,16 @@ __global__ __launch_bounds__(kBlock) void points_write_kernel(Args a, const int 
   float *dst = out + ((size_t)sp.row0 + boff) * C;
   const int nd = block_kept * C;
   for (int d = t; d < nd; d += kBlock) dst[d] = packed[d];
+}
+
+__global__ __launch_bounds__(kBlock) void points_write_kernel(Args a, const int *__restrict__ block_offs,
+                                                              const int *__restrict__ kept, float *__restrict__ out) {
+  write_block<false>(a, nullptr, block_offs, kept, out);
+}
+
+__global__ __launch_bounds__(kBlock) void points_write_paste_kernel(Args a, PasteArgs pa, const int *__restrict__ block_offs,
+                                                                    const int *__restrict__ kept, float *__restrict__ out) {
+  write_block<true>(a, &pa, block_offs, kept, out);
 }
 
 long long blocks_of(long long n) { return (n + kBlock - 1) / kBlock; }
@@ -299,6 +391,90 @@ BFHIP_EXPORT int bfhip_points_aug(const bfhip_points_aug_sample *samples_host, i
       hipLaunchKernelGGL(points_write_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, a, counts,
                          kept + first, out);
       rc = check_launch("points_aug write");
+      if (rc != BFHIP_OK) return rc;
+    }
+    counts += blocks;
+  }
+  return BFHIP_OK;
+}
+
+BFHIP_EXPORT int bfhip_points_aug_max_boxes(void) { return kMaxBoxes; }
+
+BFHIP_EXPORT int bfhip_points_aug_paste(const bfhip_points_aug_sample *samples_host,
+                                        const bfhip_points_aug_paste_desc *pastes_host, int n_samples, int C, float *out,
+                                        int32_t *kept, void *workspace, size_t workspace_bytes, void *stream) {
+  BFHIP_REQUIRE(samples_host && pastes_host && kept, "points_aug_paste: a required pointer is NULL");
+  BFHIP_REQUIRE(n_samples >= 1, "points_aug_paste: n_samples=%d", n_samples);
+  BFHIP_REQUIRE(C >= 3 && C <= kMaxC, "points_aug_paste: %d columns (3 .. %d)", C, kMaxC);
+  long long total = 0;
+  for (int i = 0; i < n_samples; ++i) {
+    const bfhip_points_aug_sample &s = samples_host[i];
+    const bfhip_points_aug_paste_desc &p = pastes_host[i];
+    BFHIP_REQUIRE(s.n >= 0 && (s.n == 0 || s.points), "points_aug_paste: sample %d: n=%d points=%p", i, s.n,
+                  (const void *)s.points);
+    BFHIP_REQUIRE((s.flags & ~63) == 0, "points_aug_paste: sample %d: flags 0x%x", i, s.flags);
+    BFHIP_REQUIRE(p.n_points >= 0 && (p.n_points == 0 || p.points), "points_aug_paste: sample %d: n_points=%d points=%p", i,
+                  p.n_points, (const void *)p.points);
+    BFHIP_REQUIRE(p.n_boxes >= 0 && p.n_boxes <= kMaxBoxes && (p.n_boxes == 0 || p.planes),
+                  "points_aug_paste: sample %d: n_boxes=%d (0 .. %d) planes=%p", i, p.n_boxes, kMaxBoxes, (const void *)p.planes);
+    BFHIP_REQUIRE((((uintptr_t)s.points | (uintptr_t)p.points | (uintptr_t)p.planes) & 3) == 0,
+                  "points_aug_paste: sample %d: a pointer is not 4-byte aligned", i);
+    total += (long long)s.n + p.n_points;
+  }
+  BFHIP_REQUIRE(total <= 0x7fffffffll, "points_aug_paste: %lld rows in all (below 2^31)", total);
+  BFHIP_REQUIRE(total == 0 || out, "points_aug_paste: out is NULL");
+  BFHIP_REQUIRE(workspace_bytes >= bfhip_points_aug_workspace_bytes(total, n_samples) && (workspace || total == 0),
+                "points_aug_paste: workspace of %zu bytes, %zu needed", workspace_bytes,
+                bfhip_points_aug_workspace_bytes(total, n_samples));
+  int *counts = (int *)workspace;
+  long long row0 = 0;
+  for (int first = 0; first < n_samples; first += kMaxSamples) {
+    const int n = n_samples - first < kMaxSamples ? n_samples - first : kMaxSamples;
+    Args a;
+    PasteArgs pa;
+    a.n_samples = n;
+    a.C = C;
+    long long blocks = 0;
+    for (int i = 0; i < kMaxSamples; ++i) {
+      Sample &d = a.s[i];
+      Paste &q = pa.p[i];
+      if (i >= n) {  // never reached by a block: block0 = the launch's block count
+        d = a.s[n - 1];
+        d.n = 0;
+        d.block0 = (int)blocks;
+        q = Paste{nullptr, nullptr, 0, 0};
+        continue;
+      }
+      const bfhip_points_aug_sample &s = samples_host[first + i];
+      const bfhip_points_aug_paste_desc &p = pastes_host[first + i];
+      const long long rows = (long long)s.n + p.n_points;
+      d.src = s.points;
+      d.n = (int)rows;  // the row space: pasted rows, then the original ones
+      d.block0 = (int)blocks;
+      d.row0 = (int)row0;
+      d.flags = s.flags;
+      for (int k = 0; k < 9; ++k) d.r[k] = s.rot[k];
+      for (int k = 0; k < 3; ++k) d.t[k] = s.trans[k];
+      d.s = s.scale;
+      for (int k = 0; k < 6; ++k) d.range[k] = s.range[k];
+      for (int k = 0; k < kRounds; ++k) d.key[k] = s.keys[k];
+      q = Paste{p.points, p.planes, p.n_points, p.n_boxes};
+      blocks += blocks_of(rows);
+      row0 += rows;
+    }
+    if (blocks > 0) {
+      hipLaunchKernelGGL(points_count_paste_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, a, pa, counts);
+      const int rc = check_launch("points_aug_paste count");
+      if (rc != BFHIP_OK) return rc;
+    }
+    hipLaunchKernelGGL(points_scan_kernel, dim3(1), dim3(kScanBlock), 0, (hipStream_t)stream, a, (int)blocks, counts,
+                       kept + first);
+    int rc = check_launch("points_aug_paste scan");
+    if (rc != BFHIP_OK) return rc;
+    if (blocks > 0) {
+      hipLaunchKernelGGL(points_write_paste_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, a, pa, counts,
+                         kept + first, out);
+      rc = check_launch("points_aug_paste write");
       if (rc != BFHIP_OK) return rc;
     }
     counts += blocks;

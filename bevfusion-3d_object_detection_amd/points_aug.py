@@ -28,6 +28,13 @@ Three ways to the points:
     (`fused_points_aug`, csrc/points_aug.hip: count, scan, ranked write -- three launches and one host read of the kept counts).
     A plan holds at most one rotate / translate / scale group, then flips, then one range filter, then a shuffle, in that order.
 
+ObjectSample (object_sample.py, in front of the chain in the LiDAR configs) adds a PASTE as the plan's first step: the sampled
+objects' points `paste_points` [m, C] and their boxes as `paste_planes(boxes)` [K, 6, 4], six inward plane equations (normal, d)
+per box by the reference's own sequence.  A point is inside a box when ((x n0 + y n1) + z n2) + d < 0 for all six planes, every
+product and sum one float32 operation; the original points inside any box are dropped, the rows become [pasted points ;
+surviving original points] and the rest of the plan runs on all of them.  On the device that is bfhip_points_aug_paste: at
+most max_boxes() boxes per sample and pasted rows with the cloud's C, otherwise the torch path.
+
 The deferred shuffle departs from the reference on purpose: `randperm(n)` needs n, which exists only after the filter ran on
 the device.  PointShuffle(defer=True) draws one 64-bit seed with `torch.randint` from torch's global generator instead and the
 order is `shuffle_permutation(seed, n_kept)`: a keyed Feistel network on the next even power of two with cycle walking, integer
@@ -58,10 +65,15 @@ _STAGES = {"rts": 1, "flip": 2, "range": 3, "shuffle": 4}
 class PointsAugPlan:
     """What the deferred point transforms of ONE sample add up to; small, picklable, left on the host by
     Det3DDataPreprocessor.cast_data.  rot float32 [3, 3] (rot_mat_T), trans float32 [3], scale float32, order "RTS" / "RST" (None:
-    no such step), flip_horizontal (y) / flip_vertical (x), range float32 [6] or None, shuffle + its 64-bit seed."""
-    __slots__ = ("rot", "trans", "scale", "order", "flip_horizontal", "flip_vertical", "range", "shuffle", "seed", "stage")
+    no such step), flip_horizontal (y) / flip_vertical (x), range float32 [6] or None, shuffle + its 64-bit seed.  ObjectSample's
+    paste, the step in front of all of these: paste_points float32 [m, C] and paste_planes float32 [K, 6, 4], both None
+    without one (such a plan's pickled state holds neither)."""
+    __slots__ = ("rot", "trans", "scale", "order", "flip_horizontal", "flip_vertical", "range", "shuffle", "seed", "stage",
+                 "paste_points", "paste_planes")
+    _PASTE = ("paste_points", "paste_planes")
 
     def __init__(self):
+        self.paste_points = self.paste_planes = None
         self.rot = np.eye(3, dtype=np.float32)
         self.trans = np.zeros(3, np.float32)
         self.scale = np.float32(1.0)
@@ -73,9 +85,10 @@ class PointsAugPlan:
         self.stage = 0
 
     def __getstate__(self):
-        return {k: getattr(self, k) for k in self.__slots__}
+        return {k: getattr(self, k) for k in self.__slots__ if k not in self._PASTE or self.paste_points is not None}
 
     def __setstate__(self, state):
+        self.paste_points = self.paste_planes = None
         for k, v in state.items():
             setattr(self, k, v)
 
@@ -84,6 +97,18 @@ class PointsAugPlan:
             raise ValueError("points_aug_plan: a %s step cannot follow what the plan already holds (one rotate / translate / scale "
                              "group, then flips, then one range filter, then a shuffle); run this pipeline with defer=False" % step)
         self.stage = _STAGES[step]
+
+    def set_paste(self, points, boxes):
+        """ObjectSample's paste: points float32 [m, C], the sampled objects' points at their boxes; boxes [K, 7+], the sampled
+        boxes.  The original points inside any of them are dropped and `points` go in front of the rest.  First step only."""
+        if self.stage != 0 or self.paste_points is not None:
+            raise ValueError("points_aug_plan: a paste must be the first step of a plan, and there is one per plan; run this "
+                             "pipeline with defer=False")
+        points = np.ascontiguousarray(np.asarray(points, dtype=np.float32))
+        if points.ndim != 2 or points.shape[1] < 3:
+            raise ValueError("set_paste: points must be [m, C] with C >= 3, got %s" % (points.shape,))
+        self.paste_points, self.paste_planes = points, paste_planes(boxes)
+        return self
 
     def set_rts(self, rot, trans, scale, order):
         if order not in ("RTS", "RST"):
@@ -204,10 +229,95 @@ def transformed_xyz(points, plan):
     return x, y, z
 
 
+def _rotate_z(corners, angles):
+    """rotation_3d_in_axis(corners [K, P, 2 or 3], angles [K], axis=2) as the reference's numpy callers reach it: through float32
+    torch tensors and the 'aij,jka->aik' einsum (M3D/structures/bbox_3d/utils.py:20-124), back in the corners' dtype."""
+    pts = torch.tensor(corners, dtype=torch.float32)
+    ang = torch.tensor(angles, dtype=torch.float32)
+    rot_sin, rot_cos = torch.sin(ang), torch.cos(ang)
+    if pts.shape[-1] == 3:
+        ones, zeros = torch.ones_like(rot_cos), torch.zeros_like(rot_cos)
+        rot = torch.stack([torch.stack([rot_cos, rot_sin, zeros]), torch.stack([-rot_sin, rot_cos, zeros]),
+                           torch.stack([zeros, zeros, ones])])
+    else:
+        rot = torch.stack([torch.stack([rot_cos, rot_sin]), torch.stack([-rot_sin, rot_cos])])
+    out = torch.einsum("aij,jka->aik", pts, rot) if pts.shape[0] else pts
+    return out.numpy().astype(corners.dtype)
+
+
+def box_corners(centers, dims, angles, origin):
+    """center_to_corner_box2d / center_to_corner_box3d(axis=2) (M3D/structures/ops/box_np_ops.py:63-201): [K, 4, 2] clockwise
+    from the minimum corner, or [K, 8, 3]; in the boxes' dtype."""
+    ndim = int(dims.shape[1])
+    norm = np.stack(np.unravel_index(np.arange(2 ** ndim), [2] * ndim), axis=1).astype(dims.dtype)
+    norm = norm[[0, 1, 3, 2]] if ndim == 2 else norm[[0, 1, 3, 2, 4, 5, 7, 6]]
+    norm = norm - np.array(origin, dtype=dims.dtype)
+    corners = dims.reshape([-1, 1, ndim]) * norm.reshape([1, 2 ** ndim, ndim])
+    corners = _rotate_z(corners, angles)
+    corners += centers.reshape([-1, 1, ndim])
+    return corners
+
+
+_SURFACES = ((0, 1, 2, 3), (7, 6, 5, 4), (0, 3, 7, 4), (1, 5, 6, 2), (0, 4, 5, 1), (3, 2, 6, 7))  # corner_to_surfaces_3d
+
+
+def paste_planes(boxes):
+    """boxes [K, 7+] (x, y, z of the bottom centre, dx, dy, dz, yaw) -> float32 [K, 6, 4]: per box the six inward plane
+    equations (n0, n1, n2, d), by the sequence points_in_rbbox takes (box_np_ops.py:354-377): center_to_corner_box3d(origin=(0.5,
+    0.5, 0), axis=2) -> corner_to_surfaces_3d -> surface_equ_3d, in the boxes' arithmetic (float32 for float32 boxes)."""
+    boxes = np.asarray(boxes)
+    if boxes.ndim != 2 or boxes.shape[1] < 7:
+        raise ValueError("boxes must be [K, 7 or more], got %s" % (boxes.shape,))
+    if not np.issubdtype(boxes.dtype, np.floating):
+        boxes = boxes.astype(np.float32)
+    if boxes.shape[0] == 0:
+        return np.zeros((0, 6, 4), np.float32)
+    corners = box_corners(boxes[:, :3], boxes[:, 3:6], boxes[:, 6], (0.5, 0.5, 0))
+    surfaces = np.array([[corners[:, i] for i in face] for face in _SURFACES]).transpose([2, 0, 1, 3])[:, :, :3, :]  # [K, 6, 3, 3]
+    vec = surfaces[:, :, :2, :] - surfaces[:, :, 1:3, :]
+    normal = np.cross(vec[:, :, 0, :], vec[:, :, 1, :])
+    d = -np.einsum("aij, aij->ai", normal, surfaces[:, :, 0, :])
+    return np.ascontiguousarray(np.concatenate([normal, d[:, :, None]], 2).astype(np.float32))
+
+
+def points_in_any_box(points, planes):
+    """bool [n]: the rows of `points` (float32 [n, C] tensor) inside any box of `planes` (float32 [K, 6, 4] tensor on the same
+    device): for all six planes ((x n0 + y n1) + z n2) + d < 0, every product and sum one float32 operation."""
+    n = int(points.shape[0])
+    xyz = points[:, :3].t().contiguous()  # [3, n]: the pairs as [K, n], points along the contiguous axis
+    step = 16384 if points.device.type == "cpu" else max(n, 1)  # on the host: temporaries that stay in the cache
+    pairs = []
+    for s in range(0, n, step):  # two opposite faces, every (box, point) pair: a slab per box, which few pairs are in
+        x, y, z = xyz[0:1, s:s + step], xyz[1:2, s:s + step], xyz[2:3, s:s + step]
+        pl = planes[:, 0, :, None]
+        inside = (((x * pl[:, 0] + y * pl[:, 1]) + z * pl[:, 2]) + pl[:, 3]) < 0
+        pl = planes[:, 1, :, None]
+        inside &= (((x * pl[:, 0] + y * pl[:, 1]) + z * pl[:, 2]) + pl[:, 3]) < 0
+        b, p = torch.nonzero(inside, as_tuple=True)
+        pairs.append((b, p + s))
+    bi = torch.cat([b for b, _ in pairs]) if pairs else torch.zeros(0, dtype=torch.int64, device=points.device)
+    pi = torch.cat([p for _, p in pairs]) if pairs else bi
+    x, y, z = points[pi, 0], points[pi, 1], points[pi, 2]
+    for k in range(2, 6):  # the other four faces for those pairs only: the same operations on the same operands
+        pl = planes[bi, k, :]
+        keep = (((x * pl[:, 0] + y * pl[:, 1]) + z * pl[:, 2]) + pl[:, 3]) < 0
+        pi, bi, x, y, z = pi[keep], bi[keep], x[keep], y[keep], z[keep]
+    out = torch.zeros(points.shape[0], dtype=torch.bool, device=points.device)
+    out[pi] = True
+    return out
+
+
 def torch_points_aug(points, plan, return_mask=False):
     """points [n, C] (tensor on any device, or array) + PointsAugPlan -> float32 [kept, C] on the points' device: the
-    specification csrc/points_aug.hip restates bit for bit.  return_mask: also the bool [n] of the rows the filter kept."""
+    specification csrc/points_aug.hip restates bit for bit.  return_mask: also the bool of the rows the filter kept (with a
+    paste: of the rows [pasted points ; surviving original points], which the rest of the plan runs on)."""
     p = _as_points(points)
+    if plan.paste_points is not None:
+        pasted = torch.from_numpy(plan.paste_points).to(p.device)
+        if pasted.shape[1] != p.shape[1]:
+            raise ValueError("points_aug_plan: pasted points have %d columns, the cloud has %d" % (pasted.shape[1], p.shape[1]))
+        inside = points_in_any_box(p, torch.from_numpy(plan.paste_planes).to(p.device))
+        p = torch.cat([pasted, p[~inside]], 0)
     x, y, z = transformed_xyz(p, plan)
     out = torch.cat([torch.stack([x, y, z], 1), p[:, 3:]], 1)
     mask = None
@@ -232,14 +342,30 @@ class _Sample(ctypes.Structure):
                 ("keys", ctypes.c_uint32 * ROUNDS)]
 
 
-def fused_supported(points):
-    """True when bfhip_points_aug takes this batch: float32 contiguous [n, C] device tensors on one device, one C in 3 .. 8,
-    fewer than 2^31 rows in all."""
+class _Paste(ctypes.Structure):
+    """bfhip_points_aug_paste_desc (include/bevfusion_hip.h)."""
+    _fields_ = [("points", ctypes.c_void_p), ("n_points", ctypes.c_int), ("planes", ctypes.c_void_p), ("n_boxes", ctypes.c_int)]
+
+
+def max_boxes():
+    """The most pasted boxes per sample the kernels take (bfhip_points_aug_max_boxes)."""
+    return int(_lib.load().bfhip_points_aug_max_boxes())
+
+
+def fused_supported(points, plans=()):
+    """True when bfhip_points_aug / bfhip_points_aug_paste takes this batch: float32 contiguous [n, C] device tensors on one
+    device, one C in 3 .. 8, fewer than 2^31 rows in all (pasted ones included); every paste with the cloud's C and at most
+    max_boxes() boxes."""
     if not points or not all(torch.is_tensor(p) and p.is_cuda and p.dtype == torch.float32 and p.dim() == 2
                              and p.is_contiguous() and p.device == points[0].device and p.shape[1] == points[0].shape[1]
                              for p in points):
         return False
-    return 3 <= points[0].shape[1] <= 8 and sum(int(p.shape[0]) for p in points) < (1 << 31)
+    pastes = [plan for plan in plans if plan.paste_points is not None]
+    if pastes and not all(plan.paste_points.shape[1] == points[0].shape[1] and plan.paste_planes.shape[0] <= max_boxes()
+                          for plan in pastes):
+        return False
+    rows = sum(int(p.shape[0]) for p in points) + sum(int(plan.paste_points.shape[0]) for plan in pastes)
+    return 3 <= points[0].shape[1] <= 8 and rows < (1 << 31)
 
 
 def descriptors(points, plans):
@@ -255,12 +381,36 @@ def descriptors(points, plans):
     return descs
 
 
+def paste_descriptors(plans, dev):
+    """(the bfhip_points_aug_paste_desc array of a batch, the device tensor it points into): every plan's pasted rows and plane
+    table packed into ONE pinned host buffer and uploaded with ONE non-blocking copy on the current stream."""
+    parts = [a.reshape(-1) for plan in plans if plan.paste_points is not None for a in (plan.paste_points, plan.paste_planes)]
+    host = torch.empty(sum(a.size for a in parts), dtype=torch.float32, pin_memory=True)
+    if host.numel():
+        np.concatenate(parts, out=host.numpy())
+    table = torch.empty(host.numel(), dtype=torch.float32, device=dev)
+    table.copy_(host, non_blocking=True)
+    descs, at, base = (_Paste * len(plans))(), 0, table.data_ptr()
+    for d, plan in zip(descs, plans):
+        if plan.paste_points is None:
+            d.points, d.n_points, d.planes, d.n_boxes = None, 0, None, 0
+            continue
+        m, k = plan.paste_points.shape[0], plan.paste_planes.shape[0]
+        d.points, d.n_points = (base + 4 * at if m else None), m
+        at += plan.paste_points.size
+        d.planes, d.n_boxes = (base + 4 * at if k else None), k
+        at += plan.paste_planes.size
+    return descs, table
+
+
 def fused_points_aug(points, plans):
     """points: list of device float32 [n_i, C]; plans: list of PointsAugPlan -> the list of [kept_i, C] tensors, views of one
-    buffer of sum(n_i) rows.  Three launches per 16 samples, then ONE host read per batch: the B kept counts, which the views'
-    shapes need (it waits for the launches)."""
+    buffer of sum(n_i + pasted rows of i) rows.  Three launches per 16 samples, then ONE host read per batch: the B kept counts,
+    which the views' shapes need (it waits for the launches).  Plans with a paste add one host-to-device copy per batch
+    (paste_descriptors) and go through bfhip_points_aug_paste; a batch without any takes bfhip_points_aug as before."""
     B, C, dev = len(points), int(points[0].shape[1]), points[0].device
-    sizes = [int(p.shape[0]) for p in points]
+    pasted = any(plan.paste_points is not None for plan in plans)
+    sizes = [int(p.shape[0]) + (len(plan.paste_points) if plan.paste_points is not None else 0) for p, plan in zip(points, plans)]
     total = sum(sizes)
     out = torch.empty((total, C), dtype=torch.float32, device=dev)
     kept = torch.empty(B, dtype=torch.int32, device=dev)
@@ -268,8 +418,13 @@ def fused_points_aug(points, plans):
     work = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
     descs = descriptors(points, plans)
     with torch.cuda.device(dev):
-        _lib.call("bfhip_points_aug", descs, B, C, out.data_ptr() if total else None, kept.data_ptr(), work.data_ptr(), nbytes,
-                  _lib.stream_of(out))
+        if pasted:
+            pastes, table = paste_descriptors(plans, dev)  # `table` owns the device memory the descriptors point into
+            _lib.call("bfhip_points_aug_paste", descs, pastes, B, C, out.data_ptr() if total else None, kept.data_ptr(),
+                      work.data_ptr(), nbytes, _lib.stream_of(out))
+        else:
+            _lib.call("bfhip_points_aug", descs, B, C, out.data_ptr() if total else None, kept.data_ptr(), work.data_ptr(),
+                      nbytes, _lib.stream_of(out))
     counts = kept.cpu().tolist()  # the batch's one host read
     views, row = [], 0
     for n, k in zip(sizes, counts):
@@ -288,7 +443,7 @@ def process_points(points, plans):
         raise ValueError("points_aug_plan: %d plans for %d samples" % (len(plans), len(points)))
     if not all(isinstance(p, PointsAugPlan) for p in plans):
         raise TypeError("points_aug_plan: every sample needs a PointsAugPlan")
-    if ENABLED and fused_supported(points):
+    if ENABLED and fused_supported(points, plans):
         PATHS["kernel"] += 1
         return fused_points_aug(points, plans)
     PATHS["torch"] += 1
@@ -554,3 +709,6 @@ class PointShuffle:
         return data
 
     __call__ = transform
+
+
+from . import object_sample  # noqa: E402,F401  registers ObjectSample and DataBaseSampler beside the chain

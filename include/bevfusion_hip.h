@@ -791,6 +791,32 @@ size_t bfhip_points_aug_workspace_bytes(long long total_rows, int n_samples);
 int bfhip_points_aug(const bfhip_points_aug_sample *samples_host, int n_samples, int C, float *out, int32_t *kept,
                      void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * bfhip_points_aug with ObjectSample's paste (M3D/datasets/transforms/transforms_3d.py:328-460) as the step in front: the
+ *   original points inside any pasted box are dropped, the sampled objects' points are put in front of the rest, and the
+ *   chain above runs on all rows.  Same three launches per 16 samples.
+ *   pastes: n_samples descriptors in HOST memory, pastes[i] beside samples_host[i].  points: DEVICE float32 [n_points, C], the
+ *     pasted rows (already translated to their boxes).  planes: DEVICE float32 [n_boxes, 6, 4], per box six inward plane
+ *     equations (n0, n1, n2, d) (bevfusion_amd/points_aug.py: paste_planes); n_boxes <= bfhip_points_aug_max_boxes() = 64.
+ *     An original row (x, y, z) is inside box j when ((x n0 + y n1) + z n2) + d < 0 for its six planes, every product and sum
+ *     one float32 operation, on the UNtransformed coordinates; it is dropped when it is inside any box.  Pasted rows skip
+ *     that test.  Both then pass through rotate / translate / scale, the flips and the range test.
+ *   The row space of sample i is its n_points pasted rows, then its n original rows: its region of `out` starts at row
+ *     sum_{j < i} (n_j + n_points_j), kept[i] counts pasted and original rows, and without the shuffle the kept pasted rows
+ *     come first.  A sample with n_points = n_boxes = 0 behaves as in bfhip_points_aug.  sum (n + n_points) < 2^31; the
+ *     workspace is bfhip_points_aug_workspace_bytes(that sum, n_samples).
+ * --------------------------------------------------------------------------------------- */
+typedef struct bfhip_points_aug_paste_desc {
+  const float *points;
+  int n_points;
+  const float *planes;
+  int n_boxes;
+} bfhip_points_aug_paste_desc;
+int bfhip_points_aug_max_boxes(void);
+int bfhip_points_aug_paste(const bfhip_points_aug_sample *samples_host, const bfhip_points_aug_paste_desc *pastes_host,
+                           int n_samples, int C, float *out, int32_t *kept, void *workspace, size_t workspace_bytes,
+                           void *stream);
+
 #ifdef __cplusplus
 }
 #endif
