@@ -158,6 +158,8 @@ SIGNATURES = {
     "bfhip_points_aug": (_c_int, [_c_vp, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_sz, _c_vp]),
     "bfhip_points_aug_max_boxes": (_c_int, []),
     "bfhip_points_aug_paste": (_c_int, [_c_vp, _c_vp, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_sz, _c_vp]),
+    "bfhip_points_aug_max_sweeps": (_c_int, []),
+    "bfhip_points_aug_sweeps": (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_sz, _c_vp]),
 }
 
 

@@ -27,6 +27,17 @@
 // first such plane -- and then passes the chain above; pasted rows skip the box test.  Scan, ranks and shuffle do not change:
 // they see one sample of m + n rows.
 //
+// LoadPointsFromMultiSweeps (bfhip_points_aug_sweeps) is a second compile-time variant, HasSweeps, alone or with HasPaste; the
+// instantiations without it are what the two entries above launch, as before.  A sample's own rows are then [keyframe ; sweep
+// 1 ; ... ; sweep S], still ONE contiguous buffer (stage_rows / stage_rows_paste do not change), cut into at most kMaxSegments
+// segments {first row, flags, dt, radius, double m[9], double t[3]} (112 B).  The tables live in device memory -- 16 x 16 of
+// them would not fit the kernel arguments -- and only a pointer and a count per sample travel beside Args / PasteArgs; a block
+// puts its sample's table into LDS (1.75 KB at the cap) with the rows.  Thread t finds its row's segment by a walk over the
+// boundaries in LDS (a block generally straddles some), drops the row when |x| < radius and |y| < radius on the raw floats,
+// multiplies by lidar2sensor in float64 (__dmul_rn / __dadd_rn: (x m0j + y m1j) + z m2j, rounded to float32, minus t_j in
+// float64, rounded again -- the reference's numpy expression, operation for operation) and writes dt into column 4 of its row in
+// the tile.  The box test of a paste then runs on these xyz.  Pasted rows are in no segment.
+//
 // perm(r), n = kept count: a balanced Feistel network of kRounds rounds on 2 * h bits, h = max(1, ceil(bitlength(n - 1) / 2)),
 // walked until the value is below n (cycle walking: the network is a bijection of [0, 4^h) whatever the round function, so the
 // walk follows the cycle of r, which comes back to r < n: it terminates, and the restriction is a bijection of [0, n)).  Round
@@ -68,7 +79,21 @@ struct Paste {
 struct PasteArgs {
   Paste p[kMaxSamples];
 };
-static_assert(sizeof(Args) + sizeof(PasteArgs) + 3 * sizeof(void *) <= 4096, "kernel arguments: HIP passes at most 4 KB");
+// the sweep step of one sample: nseg segments in device memory (nseg = 0: the sample has none)
+constexpr int kMaxSegments = BFHIP_POINTS_AUG_MAX_SEGMENTS;
+enum : int { kRemoveClose = 1, kToSensor = 2 };
+using Segment = bfhip_points_aug_segment;
+constexpr int kSegmentDwords = sizeof(Segment) / 4;
+static_assert(sizeof(Segment) == 112 && alignof(Segment) == 8, "segment layout: 4 dwords, then 12 doubles");
+struct Sweeps {
+  const Segment *seg;
+  int nseg;
+};
+struct SweepArgs {
+  Sweeps w[kMaxSamples];
+};
+static_assert(sizeof(Args) + sizeof(PasteArgs) + sizeof(SweepArgs) + 3 * sizeof(void *) <= 4096,
+              "kernel arguments: HIP passes at most 4 KB");
 
 __device__ __forceinline__ uint32_t mix32(uint32_t x) {
   x = ((x >> 16) ^ x) * 0x45d9f3bu;
@@ -166,14 +191,55 @@ __device__ __forceinline__ bool inside_any_box(const float *planes, int K, float
   return false;
 }
 
-// One block of the count kernel.  HasPaste: the sample's row space is its m pasted rows, then its n original rows (sp.n = m +
+// the sample's segment table into LDS as dwords (with the rows, before the block's barrier); fields are read back by dword
+__device__ __forceinline__ void stage_segments(const Sweeps &sw, uint32_t *segs) {
+  const uint32_t *src = (const uint32_t *)sw.seg;
+  const int nd = sw.nseg * kSegmentDwords;
+  for (int d = threadIdx.x; d < nd; d += kBlock) segs[d] = src[d];
+}
+
+// double k of a staged segment (m[0..8], t[0..2]): dwords 4 + 2 k (low half) and 5 + 2 k
+__device__ __forceinline__ double segment_double(const uint32_t *sg, int k) {
+  return __hiloint2double((int)sg[5 + 2 * k], (int)sg[4 + 2 * k]);
+}
+
+// The sweep step of row r of the sample's own rows: its segment by a walk over the boundaries (they do not decrease; an empty
+// segment shares its successor's: the last one wins), the remove-close test on the raw x, y, xyz through lidar2sensor in float64,
+// and the segment's dt.  False: the row is removed.
+__device__ __forceinline__ bool sweep_row(const uint32_t *segs, int nseg, long long r, float &x, float &y, float &z, float &dt) {
+  int s = 0;
+  for (int k = 1; k < nseg; ++k)
+    if ((int)segs[k * kSegmentDwords] <= r) s = k;
+  const uint32_t *sg = segs + s * kSegmentDwords;
+  const int f = (int)sg[1];
+  const float radius = __uint_as_float(sg[3]);
+  dt = __uint_as_float(sg[2]);
+  const bool close = (f & kRemoveClose) && fabsf(x) < radius && fabsf(y) < radius;
+  if (f & kToSensor) {
+    const double dx = (double)x, dy = (double)y, dz = (double)z;
+    float v[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const float w = (float)__dadd_rn(__dadd_rn(__dmul_rn(dx, segment_double(sg, j)), __dmul_rn(dy, segment_double(sg, 3 + j))),
+                                       __dmul_rn(dz, segment_double(sg, 6 + j)));
+      v[j] = (float)__dadd_rn((double)w, -segment_double(sg, 9 + j));
+    }
+    x = v[0], y = v[1], z = v[2];
+  }
+  return !close;
+}
+
+// One block of the count kernel.  HasSweeps: the sample's own rows go through sweep_row first (segment table in LDS once per
+// block; a removed row is not kept).  HasPaste: the sample's row space is its m pasted rows, then its n original rows (sp.n = m +
 // n), the block's run of rows may straddle the boundary, the plane table goes to LDS once per block and an original row inside
 // any box is not kept.
-template <bool HasPaste>
-__device__ __forceinline__ void count_block(const Args &a, const PasteArgs *pa, int *__restrict__ block_counts) {
+template <bool HasPaste, bool HasSweeps>
+__device__ __forceinline__ void count_block(const Args &a, const PasteArgs *pa, const SweepArgs *wa,
+                                            int *__restrict__ block_counts) {
   __shared__ float tile[kBlock * kMaxC];
   __shared__ int wsum[kWaves];
   __shared__ float planes[HasPaste ? kMaxBoxes * 24 : 1];  // without a paste: unused, and gone from the kernel
+  __shared__ uint32_t segs[HasSweeps ? kMaxSegments * kSegmentDwords : 1];
   const int si = sample_of_block(a, blockIdx.x);
   const Sample &sp = a.s[si];
   const long long first = (long long)(blockIdx.x - sp.block0) * kBlock;
@@ -183,15 +249,22 @@ __device__ __forceinline__ void count_block(const Args &a, const PasteArgs *pa, 
   } else {
     stage_rows(sp.src, first, rows, a.C, tile);
   }
+  if constexpr (HasSweeps) stage_segments(wa->w[si], segs);
   __syncthreads();
   const int t = threadIdx.x;
   bool keep = false;
   if (t < rows) {
     float x = tile[t * a.C], y = tile[t * a.C + 1], z = tile[t * a.C + 2];
     bool dropped = false;
-    if constexpr (HasPaste) dropped = first + t >= pa->p[si].m && inside_any_box(planes, pa->p[si].K, x, y, z);
+    if constexpr (HasSweeps) {
+      long long r = first + t;  // among the sample's own rows
+      if constexpr (HasPaste) r -= pa->p[si].m;
+      float dt;
+      if (wa->w[si].nseg > 0 && r >= 0) dropped = !sweep_row(segs, wa->w[si].nseg, r, x, y, z, dt);
+    }
+    if constexpr (HasPaste) dropped = dropped || (first + t >= pa->p[si].m && inside_any_box(planes, pa->p[si].K, x, y, z));
     keep = transform(sp, x, y, z);
-    if constexpr (HasPaste) keep = keep && !dropped;
+    if constexpr (HasPaste || HasSweeps) keep = keep && !dropped;
   }
   const unsigned long long bal = __ballot(keep);
   if ((t & (kWave - 1)) == 0) wsum[t / kWave] = __popcll(bal);
@@ -204,11 +277,20 @@ __device__ __forceinline__ void count_block(const Args &a, const PasteArgs *pa, 
 }
 
 __global__ __launch_bounds__(kBlock) void points_count_kernel(Args a, int *__restrict__ block_counts) {
-  count_block<false>(a, nullptr, block_counts);
+  count_block<false, false>(a, nullptr, nullptr, block_counts);
 }
 
 __global__ __launch_bounds__(kBlock) void points_count_paste_kernel(Args a, PasteArgs pa, int *__restrict__ block_counts) {
-  count_block<true>(a, &pa, block_counts);
+  count_block<true, false>(a, &pa, nullptr, block_counts);
+}
+
+__global__ __launch_bounds__(kBlock) void points_count_sweeps_kernel(Args a, SweepArgs wa, int *__restrict__ block_counts) {
+  count_block<false, true>(a, nullptr, &wa, block_counts);
+}
+
+__global__ __launch_bounds__(kBlock) void points_count_paste_sweeps_kernel(Args a, PasteArgs pa, SweepArgs wa,
+                                                                           int *__restrict__ block_counts) {
+  count_block<true, true>(a, &pa, &wa, block_counts);
 }
 
 // exclusive scan of each sample's block counts, in place; kept[s] = the sample's total
@@ -245,13 +327,15 @@ __global__ __launch_bounds__(kScanBlock) void points_scan_kernel(Args a, int tot
   }
 }
 
-template <bool HasPaste>
-__device__ __forceinline__ void write_block(const Args &a, const PasteArgs *pa, const int *__restrict__ block_offs,
-                                            const int *__restrict__ kept, float *__restrict__ out) {
+template <bool HasPaste, bool HasSweeps>
+__device__ __forceinline__ void write_block(const Args &a, const PasteArgs *pa, const SweepArgs *wa,
+                                            const int *__restrict__ block_offs, const int *__restrict__ kept,
+                                            float *__restrict__ out) {
   __shared__ float tile[kBlock * kMaxC];
   __shared__ float packed[kBlock * kMaxC];
   __shared__ int wsum[kWaves];
   __shared__ float planes[HasPaste ? kMaxBoxes * 24 : 1];
+  __shared__ uint32_t segs[HasSweeps ? kMaxSegments * kSegmentDwords : 1];
   const int si = sample_of_block(a, blockIdx.x);
   const Sample &sp = a.s[si];
   const int C = a.C;
@@ -262,6 +346,7 @@ __device__ __forceinline__ void write_block(const Args &a, const PasteArgs *pa, 
   } else {
     stage_rows(sp.src, first, rows, C, tile);
   }
+  if constexpr (HasSweeps) stage_segments(wa->w[si], segs);
   __syncthreads();
   const int t = threadIdx.x, lane = t & (kWave - 1), wv = t / kWave;
   bool keep = false;
@@ -269,9 +354,18 @@ __device__ __forceinline__ void write_block(const Args &a, const PasteArgs *pa, 
   if (t < rows) {
     x = tile[t * C], y = tile[t * C + 1], z = tile[t * C + 2];
     bool dropped = false;
-    if constexpr (HasPaste) dropped = first + t >= pa->p[si].m && inside_any_box(planes, pa->p[si].K, x, y, z);
+    if constexpr (HasSweeps) {
+      long long r = first + t;
+      if constexpr (HasPaste) r -= pa->p[si].m;
+      if (wa->w[si].nseg > 0 && r >= 0) {
+        float dt;
+        dropped = !sweep_row(segs, wa->w[si].nseg, r, x, y, z, dt);
+        tile[t * C + 4] = dt;  // the thread's own row: it alone reads it back below (C >= 5: the entry checks)
+      }
+    }
+    if constexpr (HasPaste) dropped = dropped || (first + t >= pa->p[si].m && inside_any_box(planes, pa->p[si].K, x, y, z));
     keep = transform(sp, x, y, z);
-    if constexpr (HasPaste) keep = keep && !dropped;
+    if constexpr (HasPaste || HasSweeps) keep = keep && !dropped;
   }
   const unsigned long long bal = __ballot(keep);
   const int in_wave = __popcll(bal & ((1ull << lane) - 1ull));
@@ -306,12 +400,23 @@ __device__ __forceinline__ void write_block(const Args &a, const PasteArgs *pa, 
 
 __global__ __launch_bounds__(kBlock) void points_write_kernel(Args a, const int *__restrict__ block_offs,
                                                               const int *__restrict__ kept, float *__restrict__ out) {
-  write_block<false>(a, nullptr, block_offs, kept, out);
+  write_block<false, false>(a, nullptr, nullptr, block_offs, kept, out);
 }
 
 __global__ __launch_bounds__(kBlock) void points_write_paste_kernel(Args a, PasteArgs pa, const int *__restrict__ block_offs,
                                                                     const int *__restrict__ kept, float *__restrict__ out) {
-  write_block<true>(a, &pa, block_offs, kept, out);
+  write_block<true, false>(a, &pa, nullptr, block_offs, kept, out);
+}
+
+__global__ __launch_bounds__(kBlock) void points_write_sweeps_kernel(Args a, SweepArgs wa, const int *__restrict__ block_offs,
+                                                                     const int *__restrict__ kept, float *__restrict__ out) {
+  write_block<false, true>(a, nullptr, &wa, block_offs, kept, out);
+}
+
+__global__ __launch_bounds__(kBlock) void points_write_paste_sweeps_kernel(Args a, PasteArgs pa, SweepArgs wa,
+                                                                           const int *__restrict__ block_offs,
+                                                                           const int *__restrict__ kept, float *__restrict__ out) {
+  write_block<true, true>(a, &pa, &wa, block_offs, kept, out);
 }
 
 long long blocks_of(long long n) { return (n + kBlock - 1) / kBlock; }
@@ -475,6 +580,124 @@ BFHIP_EXPORT int bfhip_points_aug_paste(const bfhip_points_aug_sample *samples_h
       hipLaunchKernelGGL(points_write_paste_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, a, pa, counts,
                          kept + first, out);
       rc = check_launch("points_aug_paste write");
+      if (rc != BFHIP_OK) return rc;
+    }
+    counts += blocks;
+  }
+  return BFHIP_OK;
+}
+
+BFHIP_EXPORT int bfhip_points_aug_max_sweeps(void) { return kMaxSegments; }
+
+BFHIP_EXPORT int bfhip_points_aug_sweeps(const bfhip_points_aug_sample *samples_host,
+                                         const bfhip_points_aug_paste_desc *pastes_host,
+                                         const bfhip_points_aug_sweeps_desc *sweeps_host, int n_samples, int C, float *out,
+                                         int32_t *kept, void *workspace, size_t workspace_bytes, void *stream) {
+  BFHIP_REQUIRE(samples_host && sweeps_host && kept, "points_aug_sweeps: a required pointer is NULL");
+  BFHIP_REQUIRE(n_samples >= 1, "points_aug_sweeps: n_samples=%d", n_samples);
+  BFHIP_REQUIRE(C >= 5 && C <= kMaxC, "points_aug_sweeps: %d columns (5 .. %d: column 4 takes the time lag)", C, kMaxC);
+  long long total = 0;
+  for (int i = 0; i < n_samples; ++i) {
+    const bfhip_points_aug_sample &s = samples_host[i];
+    const bfhip_points_aug_sweeps_desc &w = sweeps_host[i];
+    BFHIP_REQUIRE(s.n >= 0 && (s.n == 0 || s.points), "points_aug_sweeps: sample %d: n=%d points=%p", i, s.n,
+                  (const void *)s.points);
+    BFHIP_REQUIRE((s.flags & ~63) == 0, "points_aug_sweeps: sample %d: flags 0x%x", i, s.flags);
+    BFHIP_REQUIRE(((uintptr_t)s.points & 3) == 0, "points_aug_sweeps: sample %d: points not 4-byte aligned", i);
+    BFHIP_REQUIRE(w.n_segments >= 0 && w.n_segments <= kMaxSegments && (w.n_segments == 0 || w.segments),
+                  "points_aug_sweeps: sample %d: n_segments=%d (0 .. %d) segments=%p", i, w.n_segments, kMaxSegments,
+                  (const void *)w.segments);
+    BFHIP_REQUIRE(((uintptr_t)w.segments & 7) == 0, "points_aug_sweeps: sample %d: segments not 8-byte aligned", i);
+    if (w.n_segments > 0) {
+      BFHIP_REQUIRE(w.first[0] == 0 && w.first[w.n_segments] == s.n,
+                    "points_aug_sweeps: sample %d: boundaries run from %d to %d, the sample's rows from 0 to %d", i, w.first[0],
+                    w.first[w.n_segments], s.n);
+      for (int k = 0; k < w.n_segments; ++k)
+        BFHIP_REQUIRE(w.first[k] <= w.first[k + 1], "points_aug_sweeps: sample %d: boundary %d (%d) is below boundary %d (%d)", i,
+                      k + 1, w.first[k + 1], k, w.first[k]);
+    }
+    total += s.n;
+    if (pastes_host) {
+      const bfhip_points_aug_paste_desc &p = pastes_host[i];
+      BFHIP_REQUIRE(p.n_points >= 0 && (p.n_points == 0 || p.points), "points_aug_sweeps: sample %d: n_points=%d points=%p", i,
+                    p.n_points, (const void *)p.points);
+      BFHIP_REQUIRE(p.n_boxes >= 0 && p.n_boxes <= kMaxBoxes && (p.n_boxes == 0 || p.planes),
+                    "points_aug_sweeps: sample %d: n_boxes=%d (0 .. %d) planes=%p", i, p.n_boxes, kMaxBoxes,
+                    (const void *)p.planes);
+      BFHIP_REQUIRE((((uintptr_t)p.points | (uintptr_t)p.planes) & 3) == 0,
+                    "points_aug_sweeps: sample %d: a paste pointer is not 4-byte aligned", i);
+      total += p.n_points;
+    }
+  }
+  BFHIP_REQUIRE(total <= 0x7fffffffll, "points_aug_sweeps: %lld rows in all (below 2^31)", total);
+  BFHIP_REQUIRE(total == 0 || out, "points_aug_sweeps: out is NULL");
+  BFHIP_REQUIRE(workspace_bytes >= bfhip_points_aug_workspace_bytes(total, n_samples) && (workspace || total == 0),
+                "points_aug_sweeps: workspace of %zu bytes, %zu needed", workspace_bytes,
+                bfhip_points_aug_workspace_bytes(total, n_samples));
+  int *counts = (int *)workspace;
+  long long row0 = 0;
+  for (int first = 0; first < n_samples; first += kMaxSamples) {
+    const int n = n_samples - first < kMaxSamples ? n_samples - first : kMaxSamples;
+    Args a;
+    PasteArgs pa;
+    SweepArgs wa;
+    a.n_samples = n;
+    a.C = C;
+    long long blocks = 0;
+    for (int i = 0; i < kMaxSamples; ++i) {
+      Sample &d = a.s[i];
+      Paste &q = pa.p[i];
+      Sweeps &g = wa.w[i];
+      if (i >= n) {  // never reached by a block: block0 = the launch's block count
+        d = a.s[n - 1];
+        d.n = 0;
+        d.block0 = (int)blocks;
+        q = Paste{nullptr, nullptr, 0, 0};
+        g = Sweeps{nullptr, 0};
+        continue;
+      }
+      const bfhip_points_aug_sample &s = samples_host[first + i];
+      q = Paste{nullptr, nullptr, 0, 0};
+      if (pastes_host) {
+        const bfhip_points_aug_paste_desc &p = pastes_host[first + i];
+        q = Paste{p.points, p.planes, p.n_points, p.n_boxes};
+      }
+      g = Sweeps{sweeps_host[first + i].segments, sweeps_host[first + i].n_segments};
+      const long long rows = (long long)s.n + q.m;
+      d.src = s.points;
+      d.n = (int)rows;  // the row space: pasted rows, then the keyframe and the sweeps
+      d.block0 = (int)blocks;
+      d.row0 = (int)row0;
+      d.flags = s.flags;
+      for (int k = 0; k < 9; ++k) d.r[k] = s.rot[k];
+      for (int k = 0; k < 3; ++k) d.t[k] = s.trans[k];
+      d.s = s.scale;
+      for (int k = 0; k < 6; ++k) d.range[k] = s.range[k];
+      for (int k = 0; k < kRounds; ++k) d.key[k] = s.keys[k];
+      blocks += blocks_of(rows);
+      row0 += rows;
+    }
+    if (blocks > 0) {
+      if (pastes_host)
+        hipLaunchKernelGGL(points_count_paste_sweeps_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, a, pa,
+                           wa, counts);
+      else
+        hipLaunchKernelGGL(points_count_sweeps_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, a, wa, counts);
+      const int rc = check_launch("points_aug_sweeps count");
+      if (rc != BFHIP_OK) return rc;
+    }
+    hipLaunchKernelGGL(points_scan_kernel, dim3(1), dim3(kScanBlock), 0, (hipStream_t)stream, a, (int)blocks, counts,
+                       kept + first);
+    int rc = check_launch("points_aug_sweeps scan");
+    if (rc != BFHIP_OK) return rc;
+    if (blocks > 0) {
+      if (pastes_host)
+        hipLaunchKernelGGL(points_write_paste_sweeps_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, a, pa,
+                           wa, counts, kept + first, out);
+      else
+        hipLaunchKernelGGL(points_write_sweeps_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, a, wa, counts,
+                           kept + first, out);
+      rc = check_launch("points_aug_sweeps write");
       if (rc != BFHIP_OK) return rc;
     }
     counts += blocks;

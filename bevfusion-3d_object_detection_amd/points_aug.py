@@ -35,6 +35,14 @@ product and sum one float32 operation; the original points inside any box are dr
 surviving original points] and the rest of the plan runs on all of them.  On the device that is bfhip_points_aug_paste: at
 most max_boxes() boxes per sample and pasted rows with the cloud's C, otherwise the torch path.
 
+LoadPointsFromMultiSweeps (loading.py, the second step of the nuScenes configs) adds the SWEEP step in front of even that:
+`points` is then [keyframe ; sweep 1 ; ... ; sweep S] as read from the files, `sweep_starts` the S + 2 row boundaries.  A sweep
+row is dropped when |x| < radius and |y| < radius (raw float32; a NaN keeps the row), its xyz become
+float32((double(x) m0j + double(y) m1j) + double(z) m2j), then float32(double(v_j) - t_j), with m, t of the float64
+`lidar2sensor` -- the reference's `p[:, :3] @ m` and `-= t`, every product and sum one float64 operation -- and column 4 becomes
+the sweep's float32 time lag (0 on the keyframe).  The box test of a paste runs on these xyz.  On the device that is
+bfhip_points_aug_sweeps: at most max_sweeps() segments (keyframe included) and C >= 5, otherwise the torch path.
+
 The deferred shuffle departs from the reference on purpose: `randperm(n)` needs n, which exists only after the filter ran on
 the device.  PointShuffle(defer=True) draws one 64-bit seed with `torch.randint` from torch's global generator instead and the
 order is `shuffle_permutation(seed, n_kept)`: a keyed Feistel network on the next even power of two with cycle walking, integer
@@ -67,13 +75,17 @@ class PointsAugPlan:
     Det3DDataPreprocessor.cast_data.  rot float32 [3, 3] (rot_mat_T), trans float32 [3], scale float32, order "RTS" / "RST" (None:
     no such step), flip_horizontal (y) / flip_vertical (x), range float32 [6] or None, shuffle + its 64-bit seed.  ObjectSample's
     paste, the step in front of all of these: paste_points float32 [m, C] and paste_planes float32 [K, 6, 4], both None
-    without one (such a plan's pickled state holds neither)."""
+    without one (such a plan's pickled state holds neither).  LoadPointsFromMultiSweeps' sweep step, in front of the paste:
+    sweep_starts int64 [S + 2] (row boundaries of keyframe and sweeps), sweep_l2s float64 [S, 4, 4] or None (no transform),
+    sweep_dt float32 [S], sweep_remove, sweep_radius float32; all None without one (and absent from the pickled state)."""
     __slots__ = ("rot", "trans", "scale", "order", "flip_horizontal", "flip_vertical", "range", "shuffle", "seed", "stage",
-                 "paste_points", "paste_planes")
+                 "paste_points", "paste_planes", "sweep_starts", "sweep_l2s", "sweep_dt", "sweep_remove", "sweep_radius")
     _PASTE = ("paste_points", "paste_planes")
+    _SWEEPS = ("sweep_starts", "sweep_l2s", "sweep_dt", "sweep_remove", "sweep_radius")
 
     def __init__(self):
         self.paste_points = self.paste_planes = None
+        self.sweep_starts = self.sweep_l2s = self.sweep_dt = self.sweep_remove = self.sweep_radius = None
         self.rot = np.eye(3, dtype=np.float32)
         self.trans = np.zeros(3, np.float32)
         self.scale = np.float32(1.0)
@@ -85,10 +97,12 @@ class PointsAugPlan:
         self.stage = 0
 
     def __getstate__(self):
-        return {k: getattr(self, k) for k in self.__slots__ if k not in self._PASTE or self.paste_points is not None}
+        return {k: getattr(self, k) for k in self.__slots__
+                if (k not in self._PASTE or self.paste_points is not None) and (k not in self._SWEEPS or self.sweep_starts is not None)}
 
     def __setstate__(self, state):
         self.paste_points = self.paste_planes = None
+        self.sweep_starts = self.sweep_l2s = self.sweep_dt = self.sweep_remove = self.sweep_radius = None
         for k, v in state.items():
             setattr(self, k, v)
 
@@ -98,9 +112,31 @@ class PointsAugPlan:
                              "group, then flips, then one range filter, then a shuffle); run this pipeline with defer=False" % step)
         self.stage = _STAGES[step]
 
+    def set_sweeps(self, starts, lidar2sensor, dt, remove_close, radius=1.0):
+        """LoadPointsFromMultiSweeps' step: the points are [keyframe ; sweep 1 ; ... ; sweep S] and starts [S + 2] their row
+        boundaries (0, the keyframe's rows, ..., all rows).  lidar2sensor float64 [S, 4, 4] (None: the sweeps are not
+        transformed -- the padded copies of a keyframe), dt [S] the sweeps' float32 time lags.  The very first step of a plan,
+        once; it does not advance `stage`, so a paste may follow."""
+        if self.stage != 0 or self.paste_points is not None or self.sweep_starts is not None:
+            raise ValueError("points_aug_plan: the sweep step must be the first step of a plan, and there is one per plan; run this "
+                             "pipeline with defer=False")
+        starts = np.ascontiguousarray(np.asarray(starts, dtype=np.int64).reshape(-1))
+        dt = np.ascontiguousarray(np.asarray(dt, dtype=np.float32).reshape(-1))
+        S = len(dt)
+        if len(starts) != S + 2 or starts[0] != 0 or (np.diff(starts) < 0).any():
+            raise ValueError("set_sweeps: starts must be %d non-decreasing row boundaries from 0, got %s" % (S + 2, starts.tolist()))
+        if lidar2sensor is not None:
+            lidar2sensor = np.ascontiguousarray(np.asarray(lidar2sensor, dtype=np.float64).reshape(-1, 4, 4))
+            if len(lidar2sensor) != S:
+                raise ValueError("set_sweeps: %d lidar2sensor matrices for %d sweeps" % (len(lidar2sensor), S))
+        self.sweep_starts, self.sweep_l2s, self.sweep_dt = starts, lidar2sensor, dt
+        self.sweep_remove, self.sweep_radius = bool(remove_close), np.float32(radius)
+        return self
+
     def set_paste(self, points, boxes):
         """ObjectSample's paste: points float32 [m, C], the sampled objects' points at their boxes; boxes [K, 7+], the sampled
-        boxes.  The original points inside any of them are dropped and `points` go in front of the rest.  First step only."""
+        boxes.  The original points inside any of them are dropped and `points` go in front of the rest.  First step only (a
+        sweep step may stand in front of it)."""
         if self.stage != 0 or self.paste_points is not None:
             raise ValueError("points_aug_plan: a paste must be the first step of a plan, and there is one per plan; run this "
                              "pipeline with defer=False")
@@ -307,11 +343,40 @@ def points_in_any_box(points, planes):
     return out
 
 
+def sweep_rows(p, plan):
+    """The sweep step of a plan on p = [keyframe ; sweep 1 ; ... ; sweep S] (float32 [n, C] tensor, C >= 5): the rows that are
+    left, sweeps through lidar2sensor, column 4 the time lag.  The arithmetic of the module docstring."""
+    starts = [int(v) for v in plan.sweep_starts]
+    if p.shape[1] < 5 or starts[-1] != p.shape[0]:
+        raise ValueError("points_aug_plan: the sweep step needs [n, C >= 5] points with n = %d rows, got %s"
+                         % (starts[-1], tuple(p.shape)))
+    radius = float(plan.sweep_radius)
+    key = p[:starts[1]].clone()
+    key[:, 4] = 0
+    parts = [key]
+    for i in range(len(starts) - 2):
+        q = p[starts[i + 1]:starts[i + 2]]
+        if plan.sweep_remove:
+            q = q[~((q[:, 0].abs() < radius) & (q[:, 1].abs() < radius))]
+        q = q.clone()
+        if plan.sweep_l2s is not None:
+            m = [[float(v) for v in row] for row in plan.sweep_l2s[i]]
+            x, y, z = q[:, 0].double(), q[:, 1].double(), q[:, 2].double()
+            for j in range(3):
+                v = ((x * m[0][j] + y * m[1][j]) + z * m[2][j]).float()
+                q[:, j] = (v.double() - m[j][3]).float()
+        q[:, 4] = float(plan.sweep_dt[i])
+        parts.append(q)
+    return torch.cat(parts, 0)
+
+
 def torch_points_aug(points, plan, return_mask=False):
     """points [n, C] (tensor on any device, or array) + PointsAugPlan -> float32 [kept, C] on the points' device: the
     specification csrc/points_aug.hip restates bit for bit.  return_mask: also the bool of the rows the filter kept (with a
-    paste: of the rows [pasted points ; surviving original points], which the rest of the plan runs on)."""
+    paste or a sweep step: of the rows [pasted points ; surviving original points], which the rest of the plan runs on)."""
     p = _as_points(points)
+    if plan.sweep_starts is not None:
+        p = sweep_rows(p, plan)
     if plan.paste_points is not None:
         pasted = torch.from_numpy(plan.paste_points).to(p.device)
         if pasted.shape[1] != p.shape[1]:
@@ -347,15 +412,44 @@ class _Paste(ctypes.Structure):
     _fields_ = [("points", ctypes.c_void_p), ("n_points", ctypes.c_int), ("planes", ctypes.c_void_p), ("n_boxes", ctypes.c_int)]
 
 
+class _Sweeps(ctypes.Structure):
+    """bfhip_points_aug_sweeps_desc (include/bevfusion_hip.h)."""
+    _fields_ = [("segments", ctypes.c_void_p), ("n_segments", ctypes.c_int), ("first", ctypes.c_int * 17)]
+
+
+# bfhip_points_aug_segment: 112 bytes, the doubles 8-byte aligned
+SEGMENT = np.dtype([("first", "<i4"), ("flags", "<i4"), ("dt", "<f4"), ("radius", "<f4"), ("m", "<f8", (9,)), ("t", "<f8", (3,))])
+
+
+def max_sweeps():
+    """The most segments per sample, keyframe included, the kernels take (bfhip_points_aug_max_sweeps)."""
+    return int(_lib.load().bfhip_points_aug_max_sweeps())
+
+
+def sweep_segments(plan):
+    """The plan's segment table, SEGMENT [S + 1]: the keyframe (flags 0, dt 0), then per sweep flags 1 (remove close) | 2
+    (transform), its dt, the 3 x 3 of lidar2sensor row-major and its translation column."""
+    S = len(plan.sweep_dt)
+    seg = np.zeros(S + 1, SEGMENT)
+    seg["first"] = plan.sweep_starts[:-1]
+    seg["radius"] = plan.sweep_radius
+    seg["flags"][1:] = (1 if plan.sweep_remove else 0) | (2 if plan.sweep_l2s is not None else 0)
+    seg["dt"][1:] = plan.sweep_dt
+    if plan.sweep_l2s is not None:
+        seg["m"][1:] = plan.sweep_l2s[:, :3, :3].reshape(S, 9)
+        seg["t"][1:] = plan.sweep_l2s[:, :3, 3]
+    return seg
+
+
 def max_boxes():
     """The most pasted boxes per sample the kernels take (bfhip_points_aug_max_boxes)."""
     return int(_lib.load().bfhip_points_aug_max_boxes())
 
 
 def fused_supported(points, plans=()):
-    """True when bfhip_points_aug / bfhip_points_aug_paste takes this batch: float32 contiguous [n, C] device tensors on one
-    device, one C in 3 .. 8, fewer than 2^31 rows in all (pasted ones included); every paste with the cloud's C and at most
-    max_boxes() boxes."""
+    """True when bfhip_points_aug / bfhip_points_aug_paste / bfhip_points_aug_sweeps takes this batch: float32 contiguous [n, C]
+    device tensors on one device, one C in 3 .. 8, fewer than 2^31 rows in all (pasted ones included); every paste with the
+    cloud's C and at most max_boxes() boxes; every sweep step with at most max_sweeps() segments, its rows the sample's, C >= 5."""
     if not points or not all(torch.is_tensor(p) and p.is_cuda and p.dtype == torch.float32 and p.dim() == 2
                              and p.is_contiguous() and p.device == points[0].device and p.shape[1] == points[0].shape[1]
                              for p in points):
@@ -363,6 +457,10 @@ def fused_supported(points, plans=()):
     pastes = [plan for plan in plans if plan.paste_points is not None]
     if pastes and not all(plan.paste_points.shape[1] == points[0].shape[1] and plan.paste_planes.shape[0] <= max_boxes()
                           for plan in pastes):
+        return False
+    swept = [(p, plan) for p, plan in zip(points, plans) if plan.sweep_starts is not None]
+    if swept and not (points[0].shape[1] >= 5 and all(len(plan.sweep_starts) - 1 <= max_sweeps() and
+                                                      int(plan.sweep_starts[-1]) == p.shape[0] for p, plan in swept)):
         return False
     rows = sum(int(p.shape[0]) for p in points) + sum(int(plan.paste_points.shape[0]) for plan in pastes)
     return 3 <= points[0].shape[1] <= 8 and rows < (1 << 31)
@@ -403,11 +501,48 @@ def paste_descriptors(plans, dev):
     return descs, table
 
 
+def sweep_descriptors(plans, dev):
+    """(the bfhip_points_aug_paste_desc array or None when no plan has a paste, the bfhip_points_aug_sweeps_desc array, the device
+    tensor both point into): paste_descriptors with the plans' segment tables in front of the paste data -- still ONE pinned
+    host buffer and ONE non-blocking copy on the current stream."""
+    tables = [sweep_segments(plan) if plan.sweep_starts is not None else None for plan in plans]
+    pasted = [plan for plan in plans if plan.paste_points is not None]
+    parts = [t.view(np.uint8) for t in tables if t is not None]
+    parts += [a.reshape(-1).view(np.uint8) for plan in pasted for a in (plan.paste_points, plan.paste_planes)]
+    host = torch.empty(sum(a.size for a in parts), dtype=torch.uint8, pin_memory=True)
+    if host.numel():
+        np.concatenate(parts, out=host.numpy())
+    table = torch.empty(host.numel(), dtype=torch.uint8, device=dev)  # the allocator's blocks are 512-byte aligned
+    table.copy_(host, non_blocking=True)
+    sweeps, at, base = (_Sweeps * len(plans))(), 0, table.data_ptr()
+    for d, t, plan in zip(sweeps, tables, plans):
+        if t is None:
+            d.segments, d.n_segments = None, 0
+            continue
+        d.segments, d.n_segments = base + at, len(t)  # 112-byte entries from an aligned base: 8-byte aligned
+        d.first[:len(t) + 1] = [int(v) for v in plan.sweep_starts]
+        at += t.nbytes
+    if not pasted:
+        return None, sweeps, table
+    pastes = (_Paste * len(plans))()
+    for d, plan in zip(pastes, plans):
+        if plan.paste_points is None:
+            d.points, d.n_points, d.planes, d.n_boxes = None, 0, None, 0
+            continue
+        m, k = plan.paste_points.shape[0], plan.paste_planes.shape[0]
+        d.points, d.n_points = (base + at if m else None), m
+        at += plan.paste_points.nbytes
+        d.planes, d.n_boxes = (base + at if k else None), k
+        at += plan.paste_planes.nbytes
+    return pastes, sweeps, table
+
+
 def fused_points_aug(points, plans):
     """points: list of device float32 [n_i, C]; plans: list of PointsAugPlan -> the list of [kept_i, C] tensors, views of one
     buffer of sum(n_i + pasted rows of i) rows.  Three launches per 16 samples, then ONE host read per batch: the B kept counts,
     which the views' shapes need (it waits for the launches).  Plans with a paste add one host-to-device copy per batch
-    (paste_descriptors) and go through bfhip_points_aug_paste; a batch without any takes bfhip_points_aug as before."""
+    (paste_descriptors) and go through bfhip_points_aug_paste; a batch without any takes bfhip_points_aug as before.  A batch
+    in which any plan has a sweep step goes through bfhip_points_aug_sweeps, its segment tables in that same one copy."""
     B, C, dev = len(points), int(points[0].shape[1]), points[0].device
     pasted = any(plan.paste_points is not None for plan in plans)
     sizes = [int(p.shape[0]) + (len(plan.paste_points) if plan.paste_points is not None else 0) for p, plan in zip(points, plans)]
@@ -418,7 +553,11 @@ def fused_points_aug(points, plans):
     work = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
     descs = descriptors(points, plans)
     with torch.cuda.device(dev):
-        if pasted:
+        if any(plan.sweep_starts is not None for plan in plans):
+            pastes, sweeps, table = sweep_descriptors(plans, dev)  # `table` owns the device memory the descriptors point into
+            _lib.call("bfhip_points_aug_sweeps", descs, pastes, sweeps, B, C, out.data_ptr() if total else None, kept.data_ptr(),
+                      work.data_ptr(), nbytes, _lib.stream_of(out))
+        elif pasted:
             pastes, table = paste_descriptors(plans, dev)  # `table` owns the device memory the descriptors point into
             _lib.call("bfhip_points_aug_paste", descs, pastes, B, C, out.data_ptr() if total else None, kept.data_ptr(),
                       work.data_ptr(), nbytes, _lib.stream_of(out))
@@ -712,3 +851,4 @@ class PointShuffle:
 
 
 from . import object_sample  # noqa: E402,F401  registers ObjectSample and DataBaseSampler beside the chain
+from . import loading  # noqa: E402,F401  registers LoadPointsFromFile and LoadPointsFromMultiSweeps in front of it

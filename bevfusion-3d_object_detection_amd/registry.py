@@ -45,7 +45,8 @@ class Registry:
 MODELS = Registry("models")
 # data pipeline steps (mmdet3d.registry.TRANSFORMS): ImageAug3D (image_aug.py) and the LiDAR chain (points_aug.py):
 # BEVFusionGlobalRotScaleTrans, GlobalRotScaleTrans, BEVFusionRandomFlip3D, PointsRangeFilter, ObjectRangeFilter,
-# ObjectNameFilter, PointShuffle; ObjectSample and its DataBaseSampler (object_sample.py)
+# ObjectNameFilter, PointShuffle; ObjectSample and its DataBaseSampler (object_sample.py); LoadPointsFromFile and
+# LoadPointsFromMultiSweeps (loading.py)
 TRANSFORMS = Registry("transforms")
 
 

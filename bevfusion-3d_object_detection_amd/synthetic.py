@@ -268,3 +268,38 @@ def bev_pool_case(seed, n, C, B, D, H, W, integer):
     else:
         x = rng.standard_normal((n, C)).astype(np.float32)
     return x, geom, rank
+
+
+def multi_sweep_sample(seed=4000, key_rows=26000, sweep_rows=26000, sweeps=9, features=5, close=0.02):
+    """One seeded multi-sweep sample as LoadPointsFromMultiSweeps meets it: dict(keyframe f32[key_rows, features], sweeps =
+    list of f32[~sweep_rows, features] (row counts vary by a few percent), lidar2sensor f64[sweeps, 4, 4] rigid (ego motion of a
+    few metres, any heading change, a little roll and pitch), timestamp, sweep_timestamps f64[sweeps] 50 ms apart).  Returns over
+    +-60 m; a fraction `close` of every cloud lies inside the 1 m square around the sensor (returns from the ego vehicle, what
+    remove_close takes out), and a few rows sit exactly on its border."""
+    rs = np.random.RandomState(seed)
+
+    def cloud(n):
+        r, az = rs.uniform(1.5, 60.0, n), rs.uniform(-math.pi, math.pi, n)
+        p = np.zeros((n, features), np.float32)
+        p[:, 0], p[:, 1], p[:, 2] = r * np.cos(az), r * np.sin(az), rs.uniform(-4.0, 2.0, n)
+        p[:, 3:] = rs.uniform(0.0, 1.0, (n, features - 3))
+        k = int(round(close * n))
+        at = rs.permutation(n)[:k + 4]
+        p[at[:k], :2] = rs.uniform(-0.999, 0.999, (k, 2))
+        p[at[k:], :2] = np.array([[1.0, 0.25], [-1.0, -0.5], [0.125, 1.0], [1.0, -1.0]], np.float32)[:len(at) - k]
+        return p
+
+    def rigid():
+        yaw, pitch, roll = rs.uniform(-math.pi, math.pi), rs.uniform(-0.03, 0.03), rs.uniform(-0.03, 0.03)
+        cz, sz, cy, sy, cx, sx = math.cos(yaw), math.sin(yaw), math.cos(pitch), math.sin(pitch), math.cos(roll), math.sin(roll)
+        m = np.eye(4)
+        m[:3, :3] = (np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1.0]]) @ np.array([[cy, 0, sy], [0, 1.0, 0], [-sy, 0, cy]]) @
+                     np.array([[1.0, 0, 0], [0, cx, -sx], [0, sx, cx]]))
+        m[:3, 3] = rs.uniform(-8.0, 8.0, 3)
+        return m
+
+    timestamp = 1533151603.547590
+    counts = [max(0, int(sweep_rows * rs.uniform(0.95, 1.05))) for _ in range(sweeps)]
+    return dict(keyframe=cloud(key_rows), sweeps=[cloud(n) for n in counts],
+                lidar2sensor=np.stack([rigid() for _ in range(sweeps)]) if sweeps else np.zeros((0, 4, 4)),
+                timestamp=timestamp, sweep_timestamps=timestamp - 0.05 * (1 + np.arange(sweeps)) + rs.uniform(-0.004, 0.004, sweeps))

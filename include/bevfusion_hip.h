@@ -817,6 +817,42 @@ int bfhip_points_aug_paste(const bfhip_points_aug_sample *samples_host, const bf
                            int n_samples, int C, float *out, int32_t *kept, void *workspace, size_t workspace_bytes,
                            void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * bfhip_points_aug / bfhip_points_aug_paste with LoadPointsFromMultiSweeps (M3D/datasets/transforms/loading.py:316-453) as the
+ *   step in front of everything: a sample's n rows are its keyframe and its sweeps as they were read from their files, one
+ *   contiguous buffer [keyframe ; sweep 1 ; ... ; sweep S], cut into n_segments <= bfhip_points_aug_max_sweeps() = 16 segments
+ *   (the keyframe is segment 0).  Same three launches per 16 samples; needs C >= 5.
+ *   segment: first = its first row (of the sample's n); flags: 1 = remove close rows, 2 = transform; dt, radius; m = the 3 x 3
+ *     of lidar2sensor, row-major; t = its translation column.  For a row (x, y, z) of the segment:
+ *       flags & 1: the row is dropped when |x| < radius and |y| < radius, on the raw float32 x, y (a NaN keeps the row);
+ *       flags & 2: v_j = (float)(((double)x * m[j] + (double)y * m[3 + j]) + (double)z * m[6 + j]), every product and sum one
+ *                  float64 operation, then v_j = (float)((double)v_j - t[j]);
+ *       column 4 = dt.
+ *     Then the box test of a paste (on these xyz; pasted rows take no part in the sweep step), then the chain.
+ *   sweeps: n_samples descriptors in HOST memory.  segments: DEVICE, 8-byte aligned, n_segments entries; first[]: the HOST copy of
+ *     the boundaries, first[0] = 0 <= first[1] <= ... <= first[n_segments] = n, which the entry checks.  n_segments = 0: the
+ *     sample has no sweep step and behaves as in bfhip_points_aug / bfhip_points_aug_paste.
+ *   pastes: NULL (no sample has a paste) or as in bfhip_points_aug_paste; row space, `out`, `kept` and the workspace as there.
+ * --------------------------------------------------------------------------------------- */
+#define BFHIP_POINTS_AUG_MAX_SEGMENTS 16
+typedef struct bfhip_points_aug_segment {
+  int first;
+  int flags;
+  float dt;
+  float radius;
+  double m[9];
+  double t[3];
+} bfhip_points_aug_segment;
+typedef struct bfhip_points_aug_sweeps_desc {
+  const bfhip_points_aug_segment *segments;
+  int n_segments;
+  int first[BFHIP_POINTS_AUG_MAX_SEGMENTS + 1];
+} bfhip_points_aug_sweeps_desc;
+int bfhip_points_aug_max_sweeps(void);
+int bfhip_points_aug_sweeps(const bfhip_points_aug_sample *samples_host, const bfhip_points_aug_paste_desc *pastes_host,
+                            const bfhip_points_aug_sweeps_desc *sweeps_host, int n_samples, int C, float *out, int32_t *kept,
+                            void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
