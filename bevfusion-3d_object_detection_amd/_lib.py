@@ -153,6 +153,8 @@ SIGNATURES = {
     "bfhip_image_aug_supported": (_c_int, [_c_int] * 8),
     "bfhip_image_aug": (_c_int, [_c_vp, _c_int, _c_int, _c_vp, _c_vp, ctypes.c_longlong, _c_int, _c_int, _c_vp, _c_int, _c_int,
                                  _c_vp, _c_vp, ctypes.c_float] + [_c_int] * 4 + [_c_vp, _c_vp]),
+    "bfhip_image_aug_masked": (_c_int, [_c_vp, _c_vp, _c_int, _c_int, _c_vp, _c_vp, ctypes.c_longlong, _c_int, _c_int, _c_vp, _c_int,
+                                        _c_int, _c_vp, _c_vp, ctypes.c_float] + [_c_int] * 4 + [_c_vp, _c_vp]),
     "bfhip_points_aug_block": (_c_int, []),
     "bfhip_points_aug_workspace_bytes": (_c_sz, [ctypes.c_longlong, _c_int]),
     "bfhip_points_aug": (_c_int, [_c_vp, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_sz, _c_vp]),

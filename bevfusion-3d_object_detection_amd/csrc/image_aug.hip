@@ -16,6 +16,12 @@
 // Launch 2: no camera of the batch rotates -> bfhip_img_preprocess on that intermediate.  Otherwise rotate_finish_kernel, the
 //   same run-of-8 lanes, arithmetic and stores, with a per-pixel gather (x, y) = ((a2 + X a0 + Y a1) >> 16, (a5 + X a3 + Y a4)
 //   >> 16), int32 with C's wrap, zero outside, for the cameras that rotate.
+// GridMask (bfhip_image_aug_masked): when a sample of the batch carries an active mask record, launch 2 is
+//   masked_finish_kernel, the finish kernel with the records of its cameras' samples as one more kernel argument.  The mask is
+//   a closed form of the record -- bands of `length` every d on an hh x ww canvas, read at the pixel's canvas point or, when the
+//   canvas rotates, through PIL's 16.16 affine with 0 outside -- so each lane computes the 8 bits of its run in registers (the
+//   row test once per lane when the canvas does not rotate) and zeroes the masked pixels between the load and the
+//   normalisation.  No mask image, no further launch or upload; without an active record the launches are as above.
 //
 // Bounds: at most kMaxTaps = 24 taps per output and in / out <= 6.25 per axis (resize >= 0.2 of any source of 39 pixels or more
 // a side); bfhip_image_aug_supported() says so and the caller serves the rest in torch.  The per-camera descriptors travel in the
@@ -169,10 +175,42 @@ struct FinishArgs {
   int swap, normalise, out_vec;
 };
 
-// O: output element (float / bf16_t); PIX: pixel-major [img, Hp, Wp, 3] output
-template <typename O, bool PIX>
-__global__ __launch_bounds__(kFinishBlock) void rotate_finish_kernel(FinishArgs a, const uint8_t *__restrict__ mid,
-                                                                     O *__restrict__ out) {
+// GridMask of one camera's sample (bfhip_grid_mask with the band counts folded in: bands_h = hh / d with use_h, otherwise 0)
+struct MaskCam {
+  int active, d, length, st_h, st_w, bands_h, bands_w, mode;
+  int hh, ww, oy, ox, rotates;
+  int a[6];
+};
+struct MaskArgs {
+  MaskCam c[kMaxCams];
+};
+
+// canvas coordinate v lies in one of the `bands` bands of `length` every d from `start` on
+__device__ __forceinline__ bool in_band(int v, int start, int d, int bands, int length) {
+  const int t = v - start;
+  if (t < 0) return false;
+  const unsigned q = (unsigned)t / (unsigned)d;
+  return q < (unsigned)bands && (unsigned)t - q * (unsigned)d < (unsigned)length;
+}
+
+// the mask's value (pixel stays) at canvas point (Y, X) of the unrotated canvas, or of the rotated one through the affine
+__device__ __forceinline__ bool mask_keeps(const MaskCam &m, int Y, int X, bool row_band) {
+  bool keep;
+  if (m.rotates) {
+    const int sx = (int)((unsigned)m.a[2] + (unsigned)X * (unsigned)m.a[0] + (unsigned)Y * (unsigned)m.a[1]) >> 16;
+    const int sy = (int)((unsigned)m.a[5] + (unsigned)X * (unsigned)m.a[3] + (unsigned)Y * (unsigned)m.a[4]) >> 16;
+    keep = sx >= 0 && sx < m.ww && sy >= 0 && sy < m.hh && !in_band(sy, m.st_h, m.d, m.bands_h, m.length) &&
+           !in_band(sx, m.st_w, m.d, m.bands_w, m.length);
+  } else {
+    keep = !row_band && !in_band(X, m.st_w, m.d, m.bands_w, m.length);
+  }
+  return m.mode ? !keep : keep;
+}
+
+// O: output element (float / bf16_t); PIX: pixel-major [img, Hp, Wp, 3] output; MASK: mk holds the cameras' grid masks
+template <typename O, bool PIX, bool MASK>
+__device__ __forceinline__ void finish_run(const FinishArgs &a, const MaskArgs *mk, const uint8_t *__restrict__ mid,
+                                           O *__restrict__ out) {
   const int img = blockIdx.y;
   const unsigned item = blockIdx.x * kFinishBlock + threadIdx.x;
   const int y = (int)(item / (unsigned)a.runs);
@@ -197,6 +235,16 @@ __global__ __launch_bounds__(kFinishBlock) void rotate_finish_kernel(FinishArgs 
     }
   }
 
+  unsigned keep = 0xffu;  // bit j: pixel j of the run keeps its value under the sample's grid mask
+  if (MASK && nvalid > 0 && mk->c[img].active) {
+    const MaskCam &m = mk->c[img];
+    const int Y = y + m.oy;
+    const bool row_band = !m.rotates && in_band(Y, m.st_h, m.d, m.bands_h, m.length);  // one test per thread
+    keep = 0;
+#pragma unroll
+    for (int j = 0; j < kRun; ++j) keep |= (mask_keeps(m, Y, x0 + j + m.ox, row_band) ? 1u : 0u) << j;
+  }
+
   float val[3][kRun];
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
@@ -214,7 +262,10 @@ __global__ __launch_bounds__(kFinishBlock) void rotate_finish_kernel(FinishArgs 
 #pragma unroll
     for (int j = 0; j < kRun; ++j) {
       float r = a.pad;
-      if (j < nvalid) r = a.normalise ? (val[c][j] - m) / sd : val[c][j];
+      if (j < nvalid) {
+        const float v = MASK && !((keep >> j) & 1u) ? 0.f : val[c][j];
+        r = a.normalise ? (v - m) / sd : v;
+      }
       val[c][j] = r;
     }
   }
@@ -233,10 +284,29 @@ __global__ __launch_bounds__(kFinishBlock) void rotate_finish_kernel(FinishArgs 
   }
 }
 
+template <typename O, bool PIX>
+__global__ __launch_bounds__(kFinishBlock) void rotate_finish_kernel(FinishArgs a, const uint8_t *__restrict__ mid,
+                                                                     O *__restrict__ out) {
+  finish_run<O, PIX, false>(a, nullptr, mid, out);
+}
+
+// the same with the samples' grid masks: a masked pixel is 0 in all three channels before the normalisation
+template <typename O, bool PIX>
+__global__ __launch_bounds__(kFinishBlock) void masked_finish_kernel(FinishArgs a, MaskArgs mk, const uint8_t *__restrict__ mid,
+                                                                     O *__restrict__ out) {
+  finish_run<O, PIX, true>(a, &mk, mid, out);
+}
+
+// mk: NULL, or the grid masks of the launch's cameras
 template <typename O>
-void launch_finish(const FinishArgs &a, int images, int pixel_major, const uint8_t *mid, void *out, hipStream_t s) {
+void launch_finish(const FinishArgs &a, const MaskArgs *mk, int images, int pixel_major, const uint8_t *mid, void *out,
+                   hipStream_t s) {
   const dim3 grid(ceil_div((long long)a.Hp * a.runs, kFinishBlock), images);
-  if (pixel_major)
+  if (mk && pixel_major)
+    hipLaunchKernelGGL((masked_finish_kernel<O, true>), grid, dim3(kFinishBlock), 0, s, a, *mk, mid, (O *)out);
+  else if (mk)
+    hipLaunchKernelGGL((masked_finish_kernel<O, false>), grid, dim3(kFinishBlock), 0, s, a, *mk, mid, (O *)out);
+  else if (pixel_major)
     hipLaunchKernelGGL((rotate_finish_kernel<O, true>), grid, dim3(kFinishBlock), 0, s, a, mid, (O *)out);
   else
     hipLaunchKernelGGL((rotate_finish_kernel<O, false>), grid, dim3(kFinishBlock), 0, s, a, mid, (O *)out);
@@ -293,6 +363,15 @@ BFHIP_EXPORT int bfhip_image_aug(const bfhip_image_aug_cam *cams_host, int n_sam
                                  const int32_t *tables_dev, long long table_ints, int fH, int fW, void *mid, int swap_rb,
                                  int normalise, const float *mean_host, const float *std_host, float pad_value, int Hp, int Wp,
                                  int out_dtype, int pixel_major, void *out, void *stream) {
+  return bfhip_image_aug_masked(cams_host, nullptr, n_samples, views, tables_host, tables_dev, table_ints, fH, fW, mid, swap_rb,
+                                normalise, mean_host, std_host, pad_value, Hp, Wp, out_dtype, pixel_major, out, stream);
+}
+
+BFHIP_EXPORT int bfhip_image_aug_masked(const bfhip_image_aug_cam *cams_host, const bfhip_grid_mask *masks_host, int n_samples,
+                                        int views, const int32_t *tables_host, const int32_t *tables_dev, long long table_ints,
+                                        int fH, int fW, void *mid, int swap_rb, int normalise, const float *mean_host,
+                                        const float *std_host, float pad_value, int Hp, int Wp, int out_dtype, int pixel_major,
+                                        void *out, void *stream) {
   BFHIP_REQUIRE(cams_host && tables_host && tables_dev && mid && out, "image_aug: a required pointer is NULL");
   BFHIP_REQUIRE(n_samples >= 1 && views >= 1 && (long long)n_samples * views <= 0x7fffffffll / 3,
                 "image_aug: n_samples=%d views=%d", n_samples, views);
@@ -314,6 +393,19 @@ BFHIP_EXPORT int bfhip_image_aug(const bfhip_image_aug_cam *cams_host, int n_sam
     rc = check_axis("y", i, tables_host, table_ints, c.v_off, c.v_taps, c.v_first, c.v_count, c.crop[1], fH, c.h, kTH, kMaxSpanY);
     if (rc != BFHIP_OK) return rc;
     any_rotates = any_rotates || c.rotates != 0;
+  }
+  bool any_mask = false;
+  for (int i = 0; masks_host && i < n_samples; ++i) {
+    const bfhip_grid_mask &g = masks_host[i];
+    if (!g.active) continue;
+    BFHIP_REQUIRE(g.d >= 2 && g.length >= 1 && g.length < g.d && g.st_h >= 0 && g.st_h < g.d && g.st_w >= 0 && g.st_w < g.d,
+                  "image_aug: sample %d grid mask: d=%d length=%d st_h=%d st_w=%d (d >= 2, 1 <= length < d, 0 <= st < d)", i, g.d,
+                  g.length, g.st_h, g.st_w);
+    BFHIP_REQUIRE(g.hh >= 1 && g.ww >= 1 && g.crop[0] >= 0 && g.crop[1] >= 0 && (long long)g.crop[0] + fH <= g.hh &&
+                      (long long)g.crop[1] + fW <= g.ww,
+                  "image_aug: sample %d grid mask: window [%d, +%d) x [%d, +%d) outside the canvas %d x %d", i, g.crop[0], fH,
+                  g.crop[1], fW, g.hh, g.ww);
+    any_mask = true;
   }
 
   const dim3 tiles(ceil_div(fW, kTW), ceil_div(fH, kTH));
@@ -338,7 +430,7 @@ BFHIP_EXPORT int bfhip_image_aug(const bfhip_image_aug_cam *cams_host, int n_sam
     if (rc != BFHIP_OK) return rc;
   }
 
-  if (!any_rotates) {  // the second launch is the preprocessing kernel itself on the uint8 intermediate
+  if (!any_rotates && !any_mask) {  // the second launch is the preprocessing kernel itself on the uint8 intermediate
     std::vector<bfhip_img_desc> descs(n_samples);  // bfhip_img_preprocess cuts a long list into launches itself
     for (int i = 0; i < n_samples; ++i) {
       descs[i].data = (const uint8_t *)mid + (size_t)i * views * 3 * fH * fW;
@@ -360,18 +452,30 @@ BFHIP_EXPORT int bfhip_image_aug(const bfhip_image_aug_cam *cams_host, int n_sam
   fa.swap = swap_rb ? 1 : 0;
   fa.normalise = normalise ? 1 : 0;
   const size_t cam_bytes = (size_t)3 * Hp * Wp * (out_dtype == 1 ? 2 : 4);
+  MaskArgs ma;
   for (int first = 0; first < cams; first += kMaxCams) {
     const int n = cams - first < kMaxCams ? cams - first : kMaxCams;
     for (int i = 0; i < kMaxCams; ++i) {
-      const bfhip_image_aug_cam &c = cams_host[first + (i < n ? i : 0)];
+      const int cam = first + (i < n ? i : 0);
+      const bfhip_image_aug_cam &c = cams_host[cam];
       fa.c[i].rotates = c.rotates ? 1 : 0;
       for (int k = 0; k < 6; ++k) fa.c[i].a[k] = c.a[k];
+      if (!any_mask) continue;
+      const bfhip_grid_mask &g = masks_host[cam / views];  // the mask is the sample's: a chunk may begin inside one
+      MaskCam &m = ma.c[i];
+      m.active = g.active ? 1 : 0;
+      m.d = g.active ? g.d : 1, m.length = g.length, m.st_h = g.st_h, m.st_w = g.st_w;
+      m.bands_h = g.active && g.use_h ? g.hh / g.d : 0, m.bands_w = g.active && g.use_w ? g.ww / g.d : 0;
+      m.mode = g.mode ? 1 : 0;
+      m.hh = g.hh, m.ww = g.ww, m.oy = g.crop[0], m.ox = g.crop[1], m.rotates = g.rotates ? 1 : 0;
+      for (int k = 0; k < 6; ++k) m.a[k] = g.a[k];
     }
     char *dst = (char *)out + (size_t)first * cam_bytes;
     const uint8_t *src = (const uint8_t *)mid + (size_t)first * 3 * fH * fW;
     fa.out_vec = (Wp % kRun == 0 && ((uintptr_t)dst & 15) == 0) ? 1 : 0;
-    if (out_dtype == 1) launch_finish<bf16_t>(fa, n, pixel_major, src, dst, (hipStream_t)stream);
-    else launch_finish<float>(fa, n, pixel_major, src, dst, (hipStream_t)stream);
+    const MaskArgs *mk = any_mask ? &ma : nullptr;
+    if (out_dtype == 1) launch_finish<bf16_t>(fa, mk, n, pixel_major, src, dst, (hipStream_t)stream);
+    else launch_finish<float>(fa, mk, n, pixel_major, src, dst, (hipStream_t)stream);
     const int rc = check_launch("image_aug finish");
     if (rc != BFHIP_OK) return rc;
   }

@@ -11,7 +11,9 @@ own keywords) -- the form ResNet50.forward would otherwise make with one more pa
 
 `inputs["img_aug_plan"]` (image_aug.ImageAug3D(defer=True)): `img` then holds the RAW uint8 frames [N, H, W, 3] per sample and the
 resize / crop / flip / rotate of ImageAug3D runs on the device in front of the same stores (`process_frames`, csrc/image_aug.hip;
-BFHIP_IMG_AUG=0 or a CPU batch: image_aug.torch_image_aug, then the path below).
+BFHIP_IMG_AUG=0 or a CPU batch: image_aug.torch_image_aug, then the path below).  A plan that carries a GridMask record
+(image_aug.GridMask(defer=True): `plan.grid_mask`) has that mask applied on either path, after the frame's own flip and rotation
+and before normalise and pad.
 
 `inputs["points_aug_plan"]` (the point transforms of points_aug.py with defer=True): `points` then holds the loaded points and the
 rotate / scale / translate, flips, range filter and shuffle of the plans run on the device (`process_points`, csrc/points_aug.hip;

@@ -16,6 +16,13 @@ Three ways to the pixels:
     uint8 frames travel to the device and Det3DDataPreprocessor runs `fused_image_aug` (csrc/image_aug.hip): resize + crop +
     flip into a uint8 intermediate, then rotate + normalise + pad + cast -- two launches and one table upload per batch.
 
+GridMask (BF/transforms_3d.py:204-288), the step behind it in the camera + LiDAR train_pipeline (ImageAug3D -> the LiDAR chain of
+points_aug.py -> GridMask -> PointShuffle), is here as well: one mask of bands per sample, a closed form of the drawn integers
+(`grid_mask_params`, `torch_grid_mask`: PIL's rotated canvas bit for bit through the same `rotation_terms`).  defer=False
+multiplies the augmented float32 frames as the reference does; defer=True puts the record on the plan (`AugPlan.grid_mask`) and
+both deferred paths apply it to the uint8 result before normalise and pad -- `torch_image_aug`, and on the device the finish
+kernel of `fused_image_aug` (bfhip_image_aug_masked), without a further launch, upload or buffer.
+
 BFHIP_IMG_AUG (ships on; measured with tools/image_aug_micro.py: DESIGN.md section 6): 0 sends every deferred
 batch through `torch_image_aug` + the preprocessor's own path.  CPU tensors, non-contiguous frames and plans above the
 kernel's tap bound go that way as well.  PATHS counts the deferred batches each way took.
@@ -38,11 +45,18 @@ PRECISION_BITS = 22  # PIL's fixed point for the resampling weights
 PLAN_COLUMNS = ("newW", "newH", "crop_x", "crop_y", "flip", "rotates", "a0", "a1", "a2", "a3", "a4", "a5")
 
 
+# GridMask's record of one sample (bfhip_grid_mask, include/bevfusion_hip.h): the canvas is hh x ww, bands of `length` every `d`
+# from st_h / st_w on, the fH x fW window starts at (oy, ox), and the canvas is rotated by r degrees through a0 .. a5
+GRID_MASK_COLUMNS = ("active", "d", "length", "st_h", "st_w", "use_h", "use_w", "mode", "hh", "ww", "oy", "ox", "r", "rotates",
+                     "a0", "a1", "a2", "a3", "a4", "a5")
+
+
 class AugPlan(np.ndarray):
     """int32[N, 12] (PLAN_COLUMNS), one row per camera, with the output size as the attribute `final_dim` = (fH, fW).  A numpy
     array, so that Det3DDataPreprocessor.cast_data leaves it on the host.  `tables` (None, or what `sample_tables` made: the
     resampling tables of the sample's cameras for one source size) travels with the object through pickling, not through
-    slicing or copies; rows are not to be edited once it is set."""
+    slicing or copies; rows are not to be edited once it is set.  `grid_mask` (None, or the sample's int32[20] record of
+    GridMask(defer=True): GRID_MASK_COLUMNS) travels through pickling, slicing and copies: the mask is the sample's."""
 
     def __new__(cls, rows, final_dim):
         obj = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1, len(PLAN_COLUMNS)).view(cls)
@@ -52,14 +66,16 @@ class AugPlan(np.ndarray):
     def __array_finalize__(self, obj):
         self.final_dim = getattr(obj, "final_dim", None)
         self.tables = None
+        self.grid_mask = getattr(obj, "grid_mask", None)
 
-    def __reduce__(self):  # keep final_dim and the tables through pickling (loader workers)
+    def __reduce__(self):  # keep final_dim, the tables and the mask record through pickling (loader workers)
         fn, args, state = super().__reduce__()
-        return fn, args, (state, self.final_dim, self.tables)
+        return fn, args, (state, self.final_dim, self.tables, self.grid_mask)
 
     def __setstate__(self, state):
         super().__setstate__(state[0])
         self.final_dim, self.tables = state[1], state[2]
+        self.grid_mask = state[3] if len(state) > 3 else None  # a pickle from before the record existed
 
 
 # ---------------------------------------------------------------------------------------------- PIL's arithmetic on the host
@@ -256,7 +272,56 @@ def torch_image_aug(frames, plan, final_dim=None):
     if rows.shape != (frames.shape[0], len(PLAN_COLUMNS)):
         raise ValueError("plan %s does not fit %d frames" % (rows.shape, frames.shape[0]))
     views = [_augment_one(f, r, fH, fW) for f, r in zip(frames, rows)]
-    return torch.stack(views).permute(0, 3, 1, 2).contiguous()
+    out = torch.stack(views).permute(0, 3, 1, 2).contiguous()
+    record = getattr(plan, "grid_mask", None)
+    if record is not None and int(record[0]):  # GridMask(defer=True): one mask for every camera of the sample
+        out *= torch_grid_mask(record, fH, fW, out.device)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------- GridMask's mask
+def grid_mask_params(h, w, d, length, st_h, st_w, r, use_h=True, use_w=True, mode=0):
+    """The int32[20] record (GRID_MASK_COLUMNS) of one drawn mask on h x w images: the reference's canvas of int(1.5 h) x
+    int(1.5 w), its centre window and PIL's `rotate(r)` of that canvas as `rotation_terms`.  d .. r are the drawn integers."""
+    hh, ww = int(1.5 * h), int(1.5 * w)
+    rotates, a = rotation_terms(int(r), ww, hh)
+    rec = [1, int(d), int(length), int(st_h), int(st_w), int(bool(use_h)), int(bool(use_w)), int(mode == 1), hh, ww,
+           (hh - int(h)) // 2, (ww - int(w)) // 2, int(r), rotates] + a
+    return np.array(rec, dtype=np.int64).astype(np.int32)
+
+
+def torch_grid_mask(record, h, w, device=None):
+    """uint8 [h, w] of 0 / 1: what the reference multiplies the frames by, in integer torch operations.  Canvas point (Y, X) is
+    0 when it lies in a band -- t = Y - st_h >= 0, t // d < hh // d and t % d < length with use_h; X, st_w and ww likewise with
+    use_w -- and 1 otherwise; output (y, x) reads the canvas at (y + oy, x + ox) moved through the rotation's 16.16 affine as
+    `_augment_one` does, 0 outside the canvas; mode 1 inverts.  An inactive record gives ones."""
+    rec = dict(zip(GRID_MASK_COLUMNS, (int(v) for v in record)))
+    if not rec["active"]:
+        return torch.ones((h, w), dtype=torch.uint8, device=device)
+    Y = torch.arange(h, dtype=torch.int32, device=device)[:, None] + rec["oy"]
+    X = torch.arange(w, dtype=torch.int32, device=device)[None, :] + rec["ox"]
+    inside = None
+    if rec["rotates"]:
+        sx = (X * rec["a0"] + Y * rec["a1"] + rec["a2"]) >> 16  # int32: wraps as C does
+        sy = (X * rec["a3"] + Y * rec["a4"] + rec["a5"]) >> 16
+        inside = (sx >= 0) & (sx < rec["ww"]) & (sy >= 0) & (sy < rec["hh"])
+        X, Y = sx.clamp(0, rec["ww"] - 1), sy.clamp(0, rec["hh"] - 1)
+    d, length = rec["d"], rec["length"]
+
+    def band(v, start, size):
+        t = v - start
+        tc = t.clamp(min=0)
+        return (t >= 0) & (torch.div(tc, d, rounding_mode="floor") < size // d) & (tc % d < length)
+
+    masked = torch.zeros((h, w), dtype=torch.bool, device=device)
+    if rec["use_h"]:
+        masked = masked | band(Y, rec["st_h"], rec["hh"])
+    if rec["use_w"]:
+        masked = masked | band(X, rec["st_w"], rec["ww"])
+    keep = ~masked if inside is None else inside & ~masked
+    if rec["mode"]:
+        keep = ~keep
+    return keep.to(torch.uint8)
 
 
 # ---------------------------------------------------------------------------------------------- the fused device path
@@ -353,7 +418,8 @@ def fused_image_aug(frames, plans, final_dim=None, mean_std=None, swap=False, pa
                     out_dtype=None, channels_last=False, store=None, mid=None):
     """frames: list (one per sample) of device uint8 [N, H, W, 3]; plans: list of AugPlan -> the batch [B, N, 3, H', W'] in every
     form Det3DDataPreprocessor writes.  Two launches (resize + crop + flip into a uint8 intermediate; rotate + normalise + pad +
-    cast) and one table upload; no synchronisation.  store / mid: preallocated flat device buffers for the batch (B * N * 3 *
+    cast) and one table upload; no synchronisation.  Plans with an active GridMask record (`plan.grid_mask`) have their sample's
+    pixels masked in the second launch, the records travelling in its arguments.  store / mid: preallocated flat device buffers for the batch (B * N * 3 *
     H' * W' elements of the output dtype) and the uint8 intermediate (B * N * 3 * fH * fW) instead of fresh ones (tools, tests)."""
     fH, fW = _final_dim(plans[0], final_dim)
     B, N, dev = len(frames), int(frames[0].shape[0]), frames[0].device
@@ -375,11 +441,24 @@ def fused_image_aug(frames, plans, final_dim=None, mean_std=None, swap=False, pa
     tables_dev = torch.from_numpy(tables).pin_memory().to(dev, non_blocking=True)  # the batch's one upload
     normalise = mean_std is not None
     mean, std = (_lib.host_f32(v) for v in mean_std) if normalise else (None, None)
+    masks = mask_records(plans)
     with torch.cuda.device(dev):
-        _lib.call("bfhip_image_aug", cams, B, N, tables.ctypes.data, tables_dev.data_ptr(), int(tables.size), fH, fW,
-                  mid.data_ptr(), int(bool(swap)), int(normalise), mean, std, float(pad_value), Hp, Wp,
-                  1 if dtype == torch.bfloat16 else 0, int(bool(channels_last)), store.data_ptr(), _lib.stream_of(store))
+        _lib.call("bfhip_image_aug_masked", cams, None if masks is None else masks.ctypes.data, B, N, tables.ctypes.data,
+                  tables_dev.data_ptr(), int(tables.size), fH, fW, mid.data_ptr(), int(bool(swap)), int(normalise), mean, std,
+                  float(pad_value), Hp, Wp, 1 if dtype == torch.bfloat16 else 0, int(bool(channels_last)), store.data_ptr(),
+                  _lib.stream_of(store))
     return out
+
+
+def mask_records(plans):
+    """The batch's GridMask records as bfhip_image_aug_masked takes them: int32 [B, 20], zeros (inactive) for a sample without
+    one; None when no sample has an active one."""
+    masks = np.zeros((len(plans), len(GRID_MASK_COLUMNS)), dtype=np.int32)
+    for i, plan in enumerate(plans):
+        record = getattr(plan, "grid_mask", None)
+        if record is not None:
+            masks[i] = record
+    return masks if masks[:, 0].any() else None
 
 
 # ---------------------------------------------------------------------------------------------- the transform
@@ -442,5 +521,76 @@ class ImageAug3D:
             out.append(aug.permute(1, 2, 0).numpy().astype(np.float32))
         data["img"] = out
         return data
+
+    __call__ = transform
+
+
+@TRANSFORMS.register_module()
+class GridMask:
+    """The reference's GridMask (BF/transforms_3d.py:204-288) under its keywords: with probability `prob` every camera of the
+    sample is multiplied by one drawn mask of bands.  The np.random calls are the reference's, in its order and number, the one
+    draw of a skipped sample included.  defer=False: `data["img"]` (float32 [h, w, 3] arrays, after ImageAug3D) is multiplied
+    on the host.  defer=True (behind ImageAug3D(defer=True)): the drawn record goes onto `data["img_aug_plan"]`
+    (`plan.grid_mask`) and the deferred image path applies it, in the kernel that normalises and pads.
+
+    offset=True is not restated: the reference multiplies a [h, w, 1] numpy mask by a [h, w] torch tensor there, which only
+    broadcasts for square images."""
+
+    def __init__(self, use_h, use_w, max_epoch, rotate=1, offset=False, ratio=0.5, mode=0, prob=1.0, fixed_prob=False,
+                 defer=False):
+        if offset:
+            raise NotImplementedError("GridMask: offset=True is not supported: the reference's own code for it fails on every "
+                                      "image that is not square (a [h, w, 1] mask times a [h, w] plane)")
+        self.use_h = use_h
+        self.use_w = use_w
+        self.rotate = rotate
+        self.offset = offset
+        self.ratio = ratio
+        self.mode = mode
+        self.st_prob = prob
+        self.prob = prob
+        self.epoch = None
+        self.max_epoch = max_epoch
+        self.fixed_prob = fixed_prob
+        self.defer = bool(defer)
+
+    def set_epoch(self, epoch):
+        self.epoch = epoch
+        if not self.fixed_prob:
+            self.set_prob(self.epoch, self.max_epoch)
+
+    def set_prob(self, epoch, max_epoch):
+        self.prob = self.st_prob * epoch / max_epoch
+
+    def sample(self, h, w):
+        """The record of one applied draw on h x w images: the reference's calls after its first."""
+        d = np.random.randint(2, min(h, w))
+        if self.ratio == 1:
+            length = np.random.randint(1, d)
+        else:
+            length = min(max(int(d * self.ratio + 0.5), 1), d - 1)
+        st_h = np.random.randint(d)
+        st_w = np.random.randint(d)
+        r = np.random.randint(self.rotate)
+        return grid_mask_params(h, w, d, length, st_h, st_w, r, self.use_h, self.use_w, self.mode)
+
+    def transform(self, results):
+        plan = results.get("img_aug_plan")
+        if self.defer and plan is None:
+            raise ValueError("GridMask(defer=True) needs the img_aug_plan of ImageAug3D(defer=True) in front of it; on "
+                             "augmented frames use defer=False")
+        if not self.defer and plan is not None:
+            raise ValueError("GridMask(defer=False) behind ImageAug3D(defer=True): the frames are still raw and the mask "
+                             "would be drawn at the wrong size; use defer=True")
+        if np.random.rand() > self.prob:
+            return results
+        if self.defer:
+            plan.grid_mask = self.sample(*plan.final_dim)
+            return results
+        imgs = results["img"]
+        h, w = imgs[0].shape[0], imgs[0].shape[1]
+        mask = torch_grid_mask(self.sample(h, w), h, w).numpy().astype(np.float32)[:, :, None]
+        results.update(img=[x * mask for x in imgs])
+        return results
 
     __call__ = transform

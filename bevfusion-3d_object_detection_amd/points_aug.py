@@ -4,6 +4,8 @@
     :631-808) -> BEVFusionRandomFlip3D (BF :130-161) -> PointsRangeFilter (M3D :904-956) -> ObjectRangeFilter (:844-901) ->
     ObjectNameFilter (:959-1001) -> PointShuffle (:811-841)
 
+(the camera + LiDAR config has ImageAug3D in front of the chain and GridMask between ObjectNameFilter and PointShuffle: both are in
+image_aug.py, and GridMask draws from np.random even when its prob is 0, so it belongs in the list for the same random stream)
 under the reference's names, keywords and result keys, with the reference's np.random calls in the reference's order and its
 float32 / float64 arithmetic for `pcd_rotation`, `lidar_aug_matrix` and the boxes (a few dozen rows: always on the host).
 `points` is a float32 [n, C] tensor or array (C >= 3), `gt_bboxes_3d` a float32 [M, 7 or 9] tensor or array in LiDAR

@@ -43,7 +43,7 @@ class Registry:
 
 
 MODELS = Registry("models")
-# data pipeline steps (mmdet3d.registry.TRANSFORMS): ImageAug3D (image_aug.py) and the LiDAR chain (points_aug.py):
+# data pipeline steps (mmdet3d.registry.TRANSFORMS): ImageAug3D and GridMask (image_aug.py) and the LiDAR chain (points_aug.py):
 # BEVFusionGlobalRotScaleTrans, GlobalRotScaleTrans, BEVFusionRandomFlip3D, PointsRangeFilter, ObjectRangeFilter,
 # ObjectNameFilter, PointShuffle; ObjectSample and its DataBaseSampler (object_sample.py); LoadPointsFromFile and
 # LoadPointsFromMultiSweeps (loading.py)

@@ -758,6 +758,34 @@ int bfhip_image_aug(const bfhip_image_aug_cam *cams_host, int n_samples, int vie
                     int pixel_major, void *out, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * GridMask fused into ImageAug3D on the device: bfhip_image_aug with one mask record per sample.
+ *   masks_host: NULL, or n_samples records in HOST memory; they travel in the kernel arguments.  active == 0: the sample has
+ *     no mask.  The mask is defined on an hh x ww canvas of ones; with use_h canvas row Y is 0 when t = Y - st_h >= 0,
+ *     t / d < hh / d and t % d < length, with use_w column X likewise with st_w and ww.  Output pixel (y, x), y < fH, x < fW, of
+ *     every camera of the sample reads the canvas at (Y, X) = (y + crop[0], x + crop[1]); rotates != 0: at
+ *     ((a5 + X a3 + Y a4) >> 16, (a2 + X a0 + Y a1) >> 16) instead, int32, 0 outside the canvas (PIL's nearest rotate(r)).
+ *     mode != 0 inverts.  Where the mask is 0 the pixel's three channels are 0 before the normalisation; padding keeps
+ *     pad_value.  r is the angle in degrees the terms were made from and is not read.
+ *   Validated before anything is launched: d >= 2, 1 <= length < d, 0 <= st_h, st_w < d, hh, ww >= 1 and the fH x fW window
+ *     from crop inside the canvas: BFHIP_E_INVALID otherwise.
+ *   With masks_host NULL or no active record the launches are those of bfhip_image_aug.  Otherwise the second launch is the
+ *     finish kernel whether or not a camera rotates; no further launch, upload or buffer.
+ * --------------------------------------------------------------------------------------- */
+typedef struct bfhip_grid_mask {
+  int active;
+  int d, length, st_h, st_w;
+  int use_h, use_w, mode;
+  int hh, ww;
+  int crop[2]; /* top, left of the window in the canvas */
+  int r, rotates;
+  int a[6];
+} bfhip_grid_mask;
+int bfhip_image_aug_masked(const bfhip_image_aug_cam *cams_host, const bfhip_grid_mask *masks_host, int n_samples, int views,
+                           const int32_t *tables_host, const int32_t *tables_dev, long long table_ints, int fH, int fW, void *mid,
+                           int swap_rb, int normalise, const float *mean_host, const float *std_host, float pad_value, int Hp,
+                           int Wp, int out_dtype, int pixel_major, void *out, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * The point half of the LiDAR augmentation chain on the device (csrc/points_aug.hip): GlobalRotScaleTrans /
  *   BEVFusionGlobalRotScaleTrans, BEVFusionRandomFlip3D, PointsRangeFilter and PointShuffle
  *   (M3D/datasets/transforms/transforms_3d.py:631-956, BF/transforms_3d.py:130-201) of a whole batch in three launches per 16

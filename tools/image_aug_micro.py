@@ -23,7 +23,15 @@ rotates) and `test` (resize 0.48, no flip, no rotation).  One JSON line per plan
   pil       the reference's chain (resize, crop, transpose, rotate; Image.fromarray and np.array included) per frame on one
             host thread: median over the plan's six distinct cameras x PIL_REPEATS.  null when PIL is not installed.
 
-A missing GPU is an error.  Usage: image_aug_micro.py [OUT.json]   (default OUT: profiles/image_aug_micro.json)"""
+  grid_mask_host  (with --grid-mask) the reference's GridMask of one sample on one host thread: the numpy canvas, PIL's rotate,
+            the crop and the six float32 multiplies of 256 x 704 x 3; median over GRID_MASK_REPEATS draws.
+
+--grid-mask=plain|rotated puts an active GridMask record (image_aug.GridMask(defer=True): mode 1, both axes, ratio 0.5; rotate 1
+or 360) on every sample's plan: the kernel row then times bfhip_image_aug_masked with the records, the module row compares and
+times both paths with the mask.  --rows=kernel,module,fresh,pil limits what is measured (default: all).
+
+A missing GPU is an error.  Usage: image_aug_micro.py [--grid-mask=MODE] [--rows=LIST] [OUT.json]
+(default OUT: profiles/image_aug_micro.json)"""
 import json
 import os
 import sys
@@ -45,6 +53,7 @@ CALLS, WARMUP, TIMED = 10, 5, 30
 MODULE_CALLS = 3
 PIL_REPEATS = 5
 FRESH_WARMUP, FRESH_TIMED = 2, 15
+GRID_MASK_REPEATS = 15
 MEAN, STD = [123.675, 116.28, 103.53], [58.395, 57.12, 57.375]
 B, N, H, W, FINAL = 4, 6, 900, 1600, (256, 704)
 TRAIN = dict(resize_lim=[0.38, 0.55], bot_pct_lim=[0.0, 0.0], rot_lim=[-5.4, 5.4], rand_flip=True, is_train=True)
@@ -66,8 +75,14 @@ def window(fn, calls):
     return a.elapsed_time(b) / calls
 
 
-def make_plans(name, seed=0):
-    """Per sample (params, AugPlan): the transform's own sampler on the synthetic rig's calibration."""
+def grid_mask_cfg(mode):
+    return dict(use_h=True, use_w=True, max_epoch=6, rotate=360 if mode == "rotated" else 1, ratio=0.5, mode=1, prob=1.0,
+                fixed_prob=True)
+
+
+def make_plans(name, seed=0, grid_mask=None):
+    """Per sample (params, AugPlan): the transform's own sampler on the synthetic rig's calibration.  grid_mask ("plain" /
+    "rotated"): every plan gets a drawn GridMask record (a rotated one is redrawn until its angle is not 0)."""
     rig = synthetic.camera_rig(batch=B, seed=1, train_aug=False)
     aug = ia.ImageAug3D(final_dim=FINAL, defer=True, **(TRAIN if name == "train" else TEST))
     np.random.seed(seed)
@@ -76,6 +91,12 @@ def make_plans(name, seed=0):
         data = dict(ori_shape=(H, W), cam2img=rig["camera_intrinsics"][b], cam2lidar=rig["camera2lidar"][b])
         params = [aug.sample_augmentation(data, i) for i in range(N)]
         out.append((params, ia.make_plan(params, FINAL)))
+    if grid_mask:
+        mask = ia.GridMask(defer=True, **grid_mask_cfg(grid_mask))
+        for _, plan in out:
+            mask.transform(dict(img_aug_plan=plan))
+            while grid_mask == "rotated" and not plan.grid_mask[ia.GRID_MASK_COLUMNS.index("rotates")]:
+                mask.transform(dict(img_aug_plan=plan))
     return out
 
 
@@ -101,12 +122,17 @@ def kernel_row(dev, frames, plans, nbytes):
     mean, std = _lib.host_f32(MEAN), _lib.host_f32(STD)
     stream = _lib.stream_of(mid)
     state = {"k": 0}
+    masks = ia.mask_records(plans)
 
     def call():
         k = state["k"] = (state["k"] + 1) % sets
         cams, tables = prepared[k]
-        _lib.call("bfhip_image_aug", cams, B, N, tables.ctypes.data, tables_dev[k].data_ptr(), int(tables.size), FINAL[0], FINAL[1],
-                  mid.data_ptr(), 0, 1, mean, std, 0.0, FINAL[0], FINAL[1], 1, 1, outs[k].data_ptr(), stream)
+        tail = (B, N, tables.ctypes.data, tables_dev[k].data_ptr(), int(tables.size), FINAL[0], FINAL[1], mid.data_ptr(), 0, 1,
+                mean, std, 0.0, FINAL[0], FINAL[1], 1, 1, outs[k].data_ptr(), stream)
+        if masks is None:
+            _lib.call("bfhip_image_aug", cams, *tail)
+        else:
+            _lib.call("bfhip_image_aug_masked", cams, masks.ctypes.data, *tail)
 
     for _ in range(WARMUP):
         window(call, CALLS)
@@ -204,17 +230,53 @@ def pil_row(frame, params):
                 frames_per_s_per_core=round(1e3 / median(ms), 1), threads=1)
 
 
+def grid_mask_host_row(mode):
+    """The reference's GridMask.transform of one sample (six float32 frames of FINAL) restated with numpy and PIL, one thread."""
+    try:
+        from PIL import Image
+    except ImportError:
+        return None
+    torch.set_num_threads(1)
+    h, w = FINAL
+    hh, ww = int(1.5 * h), int(1.5 * w)
+    imgs = [np.random.RandomState(c).randint(0, 256, (h, w, 3)).astype(np.float32) for c in range(N)]
+    mask_aug = ia.GridMask(**grid_mask_cfg(mode))
+    np.random.seed(0)
+    ms = []
+    for _ in range(GRID_MASK_REPEATS):
+        rec = dict(zip(ia.GRID_MASK_COLUMNS, mask_aug.sample(h, w).tolist()))
+        t0 = time.perf_counter()
+        mask = np.ones((hh, ww), np.float32)
+        for i in range(hh // rec["d"]):
+            s = rec["d"] * i + rec["st_h"]
+            mask[s:min(s + rec["length"], hh), :] *= 0
+        for i in range(ww // rec["d"]):
+            s = rec["d"] * i + rec["st_w"]
+            mask[:, s:min(s + rec["length"], ww)] *= 0
+        mask = np.asarray(Image.fromarray(np.uint8(mask)).rotate(rec["r"]))
+        mask = mask[(hh - h) // 2:(hh - h) // 2 + h, (ww - w) // 2:(ww - w) // 2 + w].astype(np.float32)[:, :, None]
+        mask = 1 - mask
+        out = [x * mask for x in imgs]
+        ms.append((time.perf_counter() - t0) * 1e3)
+        del out
+    return dict(ms_per_sample=round(median(ms), 3), ms_per_sample_min_max=[round(min(ms), 3), round(max(ms), 3)], views=N, threads=1)
+
+
 if __name__ == "__main__":
     if not torch.cuda.is_available():
         raise SystemExit("image_aug_micro.py needs a GPU: nothing is measured without one")
     dev = torch.device("cuda:0")
+    grid_mask = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--grid-mask=")), None)
+    if grid_mask not in (None, "plain", "rotated"):
+        raise SystemExit("--grid-mask=plain or --grid-mask=rotated")
+    rows = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--rows=")), "kernel,module,fresh,pil").split(",")
     out = next((a for a in sys.argv[1:] if a.endswith(".json")), os.path.join(ROOT, "profiles", "image_aug_micro.json"))
     sets = CACHE_BYTES // (B * N * H * W * 3) + 2
     host = [np.ascontiguousarray(synthetic.camera_images_u8(B, N, H, W, seed=2000 + k).transpose(0, 1, 3, 4, 2)) for k in range(sets)]
     frames = [[t.contiguous() for t in torch.from_numpy(h).to(dev).unbind(0)] for h in host]
     lines = []
     for name in ("train", "test"):
-        drawn = make_plans(name)
+        drawn = make_plans(name, grid_mask=grid_mask)
         plans = [p for _, p in drawn]
         src_bytes, out_bytes = algorithmic_bytes(plans)
         line = dict(plan=name, batch=B, views=N, source=[H, W], final_dim=list(FINAL), output="bf16 pixel-major",
@@ -222,9 +284,12 @@ if __name__ == "__main__":
                     warmup_windows=WARMUP, timed_windows=TIMED, buffer_sets=sets, hbm_bytes_per_s=HBM_BYTES_PER_S,
                     resize=[round(float(p[0]), 4) for p in drawn[0][0]], rotating_cameras=int(sum(int(p[:, 5].sum()) for p in plans)),
                     algorithmic_mb=dict(crop_window_source=round(src_bytes / 1e6, 2), output=round(out_bytes / 1e6, 2)),
-                    kernel=kernel_row(dev, frames, plans, src_bytes + out_bytes), module=module_row(dev, frames, plans),
-                    fresh_draw_per_call=fresh_row(dev, frames) if name == "train" else None,
-                    pil_host=pil_row(host[0][0, 0], drawn[0][0]))
+                    grid_mask=grid_mask, grid_mask_records=None if grid_mask is None else ia.mask_records(plans).tolist(),
+                    kernel=kernel_row(dev, frames, plans, src_bytes + out_bytes) if "kernel" in rows else None,
+                    module=module_row(dev, frames, plans) if "module" in rows else None,
+                    fresh_draw_per_call=fresh_row(dev, frames) if name == "train" and "fresh" in rows else None,
+                    pil_host=pil_row(host[0][0, 0], drawn[0][0]) if "pil" in rows else None,
+                    grid_mask_host=grid_mask_host_row(grid_mask) if grid_mask and "pil" in rows else None)
         lines.append(line)
         print(json.dumps(line), flush=True)
     with open(out, "w") as f:
