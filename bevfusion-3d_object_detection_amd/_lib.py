@@ -162,6 +162,11 @@ SIGNATURES = {
     "bfhip_points_aug_paste": (_c_int, [_c_vp, _c_vp, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_sz, _c_vp]),
     "bfhip_points_aug_max_sweeps": (_c_int, []),
     "bfhip_points_aug_sweeps": (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_sz, _c_vp]),
+    "bfhip_query_init_supported": (_c_int, [_c_int] * 8),
+    "bfhip_query_init_workspace_bytes": (_c_sz, [_c_int] * 4),
+    "bfhip_query_init_fwd": (_c_int, [_c_vp] + [ctypes.c_longlong] * 4 + [_c_int] * 4 + [ctypes.c_uint, _c_vp, ctypes.c_longlong,
+                                      ctypes.c_longlong] + [_c_int] * 4 + [_c_vp] * 6 + [_c_sz, _c_vp]),
+    "bfhip_query_init_bwd": (_c_int, [_c_vp, _c_vp, _c_int, _c_int, _c_int, ctypes.c_longlong, _c_int, _c_vp, _c_vp]),
 }
 
 

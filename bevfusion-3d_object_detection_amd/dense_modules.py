@@ -26,6 +26,7 @@ from .bn2d import BatchNorm2dAct, BatchNormRows, bn_act
 from .conv2d import Conv2d, Conv2dHipWgrad, fp32_island
 from .linear_rows import linear_rows
 from . import attention as split_attention
+from . import query_init
 from .registry import MODELS
 
 
@@ -542,7 +543,7 @@ class BEVFusionHead(nn.Module):
                  num_decoder_layers=1, decoder_layer=dict(), num_heads=8, nms_kernel_size=3, bn_momentum=0.1,
                  common_heads=dict(center=[2, 2], height=[1, 2], dim=[3, 2], rot=[2, 2], vel=[2, 2]),
                  num_heatmap_convs=2, grid_size=(1440, 1440, 41), out_size_factor=8, train_cfg=None, test_cfg=None,
-                 bbox_coder=None,
+                 bbox_coder=None, nms_free_classes=(),
                  loss_cls=dict(type="mmdet.FocalLoss", use_sigmoid=True, gamma=2.0, alpha=0.25, reduction="mean", loss_weight=1.0),
                  loss_bbox=dict(type="mmdet.L1Loss", reduction="mean", loss_weight=0.25),
                  loss_heatmap=dict(type="mmdet.GaussianFocalLoss", reduction="mean", loss_weight=1.0), **kwargs):
@@ -577,6 +578,12 @@ class BEVFusionHead(nn.Module):
         bx, by = torch.meshgrid(torch.linspace(0, xs - 1, xs), torch.linspace(0, ys - 1, ys), indexing="ij")
         self.register_buffer("bev_pos", torch.stack([bx + 0.5, by + 0.5], 0).view(1, 2, -1).permute(0, 2, 1),
                              persistent=False)
+        self._pos_w = ys   # bev_pos[i] = (i // ys + 0.5, i % ys + 0.5)
+        # classes whose scores skip the 3x3 peak test (upstream mmdet3d: pedestrian, traffic cone; the reference has that
+        # exception commented out, BF/bevfusion_head.py:227-238, hence the empty default)
+        self.nms_free_classes = tuple(int(c) for c in nms_free_classes)
+        query_init.class_mask(self.nms_free_classes, num_classes)
+        assert not self.nms_free_classes or nms_kernel_size == 3, "nms_free_classes is implemented for the 3x3 window only"
 
     def forward(self, feats, metas=None):
         inputs = feats[0] if isinstance(feats, (list, tuple)) else feats
@@ -588,17 +595,30 @@ class BEVFusionHead(nn.Module):
         with torch.autocast("cuda", enabled=False), fp32_island(mixed):   # the reference's fp32 island (BF/bevfusion_head.py:218)
             dense_heatmap = self.heatmap_head(fusion_feat.float())
         heatmap = dense_heatmap.detach().sigmoid()
-        pad = self.nms_kernel_size // 2
-        local_max = torch.zeros_like(heatmap)
-        inner = F.max_pool2d(heatmap, kernel_size=self.nms_kernel_size, stride=1, padding=0)
-        local_max[:, :, pad:-pad, pad:-pad] = inner
-        heatmap = (heatmap * (heatmap == local_max)).reshape(B, heatmap.shape[1], -1)
-        top = heatmap.reshape(B, -1).topk(self.num_proposals, dim=-1).indices  # = argsort(descending)[:num_proposals]
-        top_class, top_index = top // heatmap.shape[-1], top % heatmap.shape[-1]
-        # the BEV rows at the proposals by indexing, not gather: two classes can pick the same cell, and gather's backward adds their
-        # gradients with atomics (a different sum from run to run); indexing's backward is a sorted, fixed-order accumulation
-        rows = flat.transpose(1, 2)[torch.arange(B, device=flat.device)[:, None], top_index]   # [B, P, C]
-        query_feat = rows.transpose(1, 2).contiguous()
+        fused = query_init.enabled() and query_init.supported(heatmap, flat, self.num_proposals, self.nms_kernel_size,
+                                                              self.nms_free_classes)
+        if fused:
+            # peaks, top-K, and every gather below in three launches with a defined tie order (csrc/query_init.hip)
+            top_class, top_index, query_pos, query_heatmap_score, rows = query_init.fused_query_init(
+                heatmap, flat, self.num_proposals, self._pos_w, self.nms_free_classes)
+            query_feat = rows.transpose(1, 2).contiguous()
+        elif self.nms_free_classes:   # the reference chain below has no such exception: the same arithmetic in torch ops
+            fused = True
+            top_class, top_index, query_pos, query_heatmap_score, rows = query_init.torch_query_init(
+                heatmap, flat, self.num_proposals, self._pos_w, self.nms_free_classes)
+            query_feat = rows.transpose(1, 2).contiguous()
+        else:
+            pad = self.nms_kernel_size // 2
+            local_max = torch.zeros_like(heatmap)
+            inner = F.max_pool2d(heatmap, kernel_size=self.nms_kernel_size, stride=1, padding=0)
+            local_max[:, :, pad:-pad, pad:-pad] = inner
+            heatmap = (heatmap * (heatmap == local_max)).reshape(B, heatmap.shape[1], -1)
+            top = heatmap.reshape(B, -1).topk(self.num_proposals, dim=-1).indices  # = argsort(descending)[:num_proposals]
+            top_class, top_index = top // heatmap.shape[-1], top % heatmap.shape[-1]
+            # the BEV rows at the proposals by indexing, not gather: two classes can pick the same cell, and gather's backward adds their
+            # gradients with atomics (a different sum from run to run); indexing's backward is a sorted, fixed-order accumulation
+            rows = flat.transpose(1, 2)[torch.arange(B, device=flat.device)[:, None], top_index]   # [B, P, C]
+            query_feat = rows.transpose(1, 2).contiguous()
         one_hot = F.one_hot(top_class, num_classes=self.num_classes)   # [B, P, classes]
         if _HEAD_ROWS and query_feat.is_cuda and self.class_encoding.kernel_size == (1,):
             # the k = 1 Conv1d over [B, classes, P] is a GEMM over the rows [B, P, classes]
@@ -606,7 +626,8 @@ class BEVFusionHead(nn.Module):
             query_feat = query_feat + enc.permute(0, 2, 1)
         else:
             query_feat = query_feat + self.class_encoding(one_hot.permute(0, 2, 1).to(query_feat.dtype))
-        query_pos = bev_pos.gather(index=top_index[:, :, None].expand(-1, -1, 2), dim=1)
+        if not fused:
+            query_pos = bev_pos.gather(index=top_index[:, :, None].expand(-1, -1, 2), dim=1)
         rets = []
         for i in range(self.num_decoder_layers):
             query_feat = self.decoder[i](query_feat, key=flat, query_pos=query_pos, key_pos=bev_pos)
@@ -614,7 +635,9 @@ class BEVFusionHead(nn.Module):
             res["center"] = res["center"] + query_pos.permute(0, 2, 1)
             rets.append(res)
             query_pos = res["center"].detach().clone().permute(0, 2, 1)
-        rets[0]["query_heatmap_score"] = heatmap.gather(index=top_index[:, None, :].expand(-1, self.num_classes, -1), dim=-1)
+        if not fused:
+            query_heatmap_score = heatmap.gather(index=top_index[:, None, :].expand(-1, self.num_classes, -1), dim=-1)
+        rets[0]["query_heatmap_score"] = query_heatmap_score
         rets[0]["dense_heatmap"] = dense_heatmap
         rets[0]["query_labels"] = top_class
         self.query_labels = top_class

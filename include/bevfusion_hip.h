@@ -881,6 +881,36 @@ int bfhip_points_aug_sweeps(const bfhip_points_aug_sample *samples_host, const b
                             const bfhip_points_aug_sweeps_desc *sweeps_host, int n_samples, int C, float *out, int32_t *kept,
                             void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Query initialisation of the TransFusion head (csrc/query_init.hip; BF/bevfusion_head.py:221-260,278-281): 3x3 peak test,
+ *   the K best masked scores of a sample and the gather of what the head reads at them.  Three launches, no host read.
+ *   h: float32 score map [B, C, H, W] with element strides h_sb, h_sc, h_sy, h_sx (NCHW or channels-last; nothing is copied).
+ *   m(b, c, y, x) = h where h > 0 and (bit c of nms_free_mask is set, or the cell is interior, 1 <= y <= H-2, 1 <= x <= W-2,
+ *     and h >= each of its 8 neighbours in its class plane); 0 elsewhere.  A NaN is never a peak and fails every comparison.
+ *   The picks of a sample are the first K of its C*H*W cells ordered by (m descending, flat = c*H*W + y*W + x ascending): equal
+ *     scores go to the lower index, and with fewer than K positive cells the zero-valued cells follow in ascending flat index
+ *     (NaN cells after all of those).  The order is a property of the input alone: the results are bit-reproducible.
+ *   flat: the BEV feature rows, element (b, cell, ch) at flat + (b * flat_sb + cell * flat_sr + ch) elements, float32
+ *     (row_dtype 0) or bf16 (1), 16-byte aligned rows.
+ *   top_class, top_index: int64 [B, K] (flat / HW, flat % HW).  query_pos: float32 [B, K, 2] =
+ *     (top_index / pos_w + 0.5, top_index % pos_w + 0.5).  query_heatmap_score: float32 [B, C, K], m of every class at the
+ *     picked cell.  rows: [B, K, Ch] dense, row_dtype.
+ *   bfhip_query_init_supported: 1 when nms_kernel_size == 3, 1 <= K <= 512, K <= C*H*W < 2^31, C <= 32, H, W >= 3 and Ch is a
+ *     whole number of 16-byte vectors of row_dtype.  workspace: bfhip_query_init_workspace_bytes(B, C, H, W), 16-byte aligned
+ *     (it holds the worst case, a constant map, where every cell is a candidate).
+ *   bfhip_query_init_bwd: d_flat [B, HW, Ch] dense = 0, then d_flat[b, top_index[b, p], :] = sum of d_rows[b, p', :] over the
+ *     picks p' of that cell in ascending p', summed in float32 and rounded once to row_dtype (memset + one launch, no atomics).
+ *     d_rows [B, K, Ch] dense, 16-byte aligned.
+ * --------------------------------------------------------------------------------------- */
+int bfhip_query_init_supported(int B, int C, int H, int W, int K, int Ch, int nms_kernel_size, int row_dtype);
+size_t bfhip_query_init_workspace_bytes(int B, int C, int H, int W);
+int bfhip_query_init_fwd(const float *h, long long h_sb, long long h_sc, long long h_sy, long long h_sx, int B, int C, int H, int W,
+                         unsigned nms_free_mask, const void *flat, long long flat_sb, long long flat_sr, int Ch, int row_dtype,
+                         int K, int pos_w, long long *top_class, long long *top_index, float *query_pos,
+                         float *query_heatmap_score, void *rows, void *workspace, size_t workspace_bytes, void *stream);
+int bfhip_query_init_bwd(const long long *top_index, const void *d_rows, int B, int K, int Ch, long long HW, int row_dtype,
+                         void *d_flat, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
