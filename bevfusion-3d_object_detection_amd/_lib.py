@@ -167,6 +167,9 @@ SIGNATURES = {
     "bfhip_query_init_fwd": (_c_int, [_c_vp] + [ctypes.c_longlong] * 4 + [_c_int] * 4 + [ctypes.c_uint, _c_vp, ctypes.c_longlong,
                                       ctypes.c_longlong] + [_c_int] * 4 + [_c_vp] * 6 + [_c_sz, _c_vp]),
     "bfhip_query_init_bwd": (_c_int, [_c_vp, _c_vp, _c_int, _c_int, _c_int, ctypes.c_longlong, _c_int, _c_vp, _c_vp]),
+    "bfhip_jpeg_parse": (_c_int, [_c_vp, _c_sz, _c_vp]),
+    "bfhip_jpeg_entropy_decode": (_c_int, [_c_vp, _c_sz, _c_vp, _c_vp, _c_sz]),
+    "bfhip_jpeg_decode": (_c_int, [_c_vp, _c_vp, _c_int, _c_vp, _c_sz, _c_vp, _c_sz, _c_vp, _c_sz, _c_vp]),
 }
 
 

@@ -19,11 +19,17 @@ and before normalise and pad.
 rotate / scale / translate, flips, range filter and shuffle of the plans run on the device (`process_points`, csrc/points_aug.hip;
 BFHIP_POINTS_AUG=0 or a CPU batch: points_aug.torch_points_aug, same bits).  Without a plan points pass through as they are.
 
+A sample of `img` that is a jpeg.JpegFrames (loading.BEVLoadMultiViewImageFromFiles(defer=True): entropy-decoded JPEG frames)
+is first decoded on the device into that raw uint8 [N, H, W, 3] block (`decode_jpeg`, csrc/jpeg.hip: one pinned upload and two
+launches for the batch; BFHIP_JPEG_DECODE=0 or a CPU module: jpeg.torch_jpeg_decode, same bits), then goes on as above: through
+`process_frames` with a plan, otherwise through `process_imgs` on its [N, 3, H, W] view.
+
 BFHIP_IMG_PREPROCESS (ships on; measured: DESIGN.md section 6): 0 selects the plain-torch restatement below, which also
 serves whatever the kernel does not take -- CPU tensors, other dtypes, non-contiguous blocks, a one-value mean.
 """
 import os
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 from torch import nn
@@ -215,6 +221,28 @@ class Det3DDataPreprocessor(nn.Module):
         image_aug.PATHS["torch"] += 1
         return self.process_imgs([image_aug.torch_image_aug(f, p) for f, p in zip(frames, plans)])
 
+    def decode_jpeg(self, img, planar):
+        """The JpegFrames samples of `img` decoded into uint8 [N, H, W, 3] blocks on the module's device, all in one batch (a
+        numpy uint8 [N, H, W, 3] block -- a sample the loader decoded on the host -- is moved there); with `planar` those
+        blocks as their [N, 3, H, W] views.  Anything else is returned as it came."""
+        from . import jpeg
+        if isinstance(img, jpeg.JpegFrames):
+            img = [img]
+        if not isinstance(img, (list, tuple)):
+            return img
+        img = list(img)
+        raw = [i for i, s in enumerate(img) if isinstance(s, np.ndarray) and s.dtype == np.uint8 and s.ndim == 4 and s.shape[-1] == 3]
+        deferred = [i for i, s in enumerate(img) if isinstance(s, jpeg.JpegFrames)]
+        for i in raw:
+            img[i] = torch.from_numpy(img[i]).to(self.device)
+        if deferred:
+            for i, block in zip(deferred, jpeg.decode_frames([img[i] for i in deferred], self.device)):
+                img[i] = block
+        if planar:
+            for i in raw + deferred:
+                img[i] = img[i].permute(0, 3, 1, 2)
+        return img
+
     def process_points(self, points, plans):
         """Deferred GlobalRotScaleTrans / RandomFlip3D / PointsRangeFilter / PointShuffle: points = per sample the loaded
         [n, C] tensor, plans = per sample the PointsAugPlan the transforms wrote with defer=True -> the list of float32
@@ -239,6 +267,8 @@ class Det3DDataPreprocessor(nn.Module):
             else:
                 batch_inputs["points"] = inputs["points"]
         if "img" in inputs:
+            # entropy-decoded JPEG frames first become the raw blocks: [N, H, W, 3] for a plan, [N, 3, H, W] views without one
+            inputs = dict(inputs, img=self.decode_jpeg(inputs["img"], planar=inputs.get("img_aug_plan") is None))
             if inputs.get("img_aug_plan") is not None:  # raw frames + ImageAug3D(defer=True)'s plans: augment on the device
                 batch = self.process_frames(inputs["img"], inputs["img_aug_plan"])
                 sizes = [batch.shape[-2:]] * batch.shape[0]  # every sample is final_dim, padded to the divisor

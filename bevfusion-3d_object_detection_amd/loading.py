@@ -15,10 +15,25 @@ defer=False runs that step on the host.  defer=True leaves `points` as ONE conti
 sweeps' raw rows] -- untouched file contents: the loader's worker does nothing but np.fromfile and one concatenate -- and writes
 the step into data["points_aug_plan"], in front of ObjectSample's paste and the chain; Det3DDataPreprocessor.process_points runs
 it on the device with the rest of the plan (csrc/points_aug.hip).  Deferral needs use_dim == range(load_dim), 5 <= load_dim <= 8.
+
+BEVLoadMultiViewImageFromFiles (BF/loading.py:13-208, keywords of mmdet3d's LoadMultiViewImageFromFiles) is the first step of
+the camera side.  From `images` (per camera img_path, cam2img, lidar2cam) it makes cam2img / lidar2cam / cam2lidar / lidar2img /
+ori_cam2img with the reference's dtypes and operation order -- lidar2cam in float32, cam2lidar a float64 eye(4) filled from the
+float32 transpose and -R^T t, cam2img a float32 eye(4) with the 3x3 block, lidar2img their float32 product -- and, with
+num_ref_frames > 0, the reference's frame choice with its np.random.choice calls in its order (the files are then still
+taken from `images`, as there).  The frames are JPEG files decoded by this package's own decoder (jpeg.py: bit for bit
+Pillow's, which the reference calls): defer=False leaves `img` as the list of uint8 [H, W, 3] arrays (float32 with to_float32),
+zero-padded to the largest; defer=True runs only the entropy stage in the worker and leaves a jpeg.JpegFrames -- headers and
+coefficients, nothing decoded -- for Det3DDataPreprocessor to decode on the device.  A sample with a frame the fused decoder
+does not take is decoded on the host with Pillow (one warning) and is the uint8 [N, H, W, 3] block instead.
 """
+import copy
+import warnings
+
 import numpy as np
 import torch
 
+from . import jpeg
 from . import points_aug as pa
 from .registry import TRANSFORMS
 
@@ -116,5 +131,145 @@ class LoadPointsFromMultiSweeps:
             out = out[:, self.use_dim]
         data["points"] = out if was_tensor else out.numpy()
         return data
+
+    __call__ = transform
+
+
+_warned_fallback = False
+
+
+def _host_decode(stream, reason):
+    """Pillow's decode of a stream the fused decoder does not take: uint8 [H, W, 3]."""
+    global _warned_fallback
+    if not _warned_fallback:
+        _warned_fallback = True
+        warnings.warn("BEVLoadMultiViewImageFromFiles: a frame is not taken by the fused JPEG decoder (%s); such samples are "
+                      "decoded on the host with Pillow" % reason)
+    import io
+    try:
+        from PIL import Image
+    except ImportError as e:
+        raise RuntimeError("a frame needs the host JPEG decoder (%s) and Pillow is not installed" % reason) from e
+    return np.asarray(Image.open(io.BytesIO(bytes(stream))).convert("RGB"))
+
+
+def _pad_to(img, shape):
+    """mmcv.impad(img, shape=shape, pad_val=0): zeros at the bottom and right."""
+    if tuple(img.shape[:2]) == tuple(shape):
+        return img
+    out = np.zeros((shape[0], shape[1]) + img.shape[2:], dtype=img.dtype)
+    out[:img.shape[0], :img.shape[1]] = img
+    return out
+
+
+@TRANSFORMS.register_module()
+class BEVLoadMultiViewImageFromFiles:
+    """See the module docstring.  color_type: 'unchanged' or 'color', on three-component files; backend_args is accepted and
+    ignored (files are local)."""
+
+    def __init__(self, to_float32=False, color_type="unchanged", backend_args=None, num_views=5, num_ref_frames=-1,
+                 test_mode=False, set_default_scale=True, defer=False):
+        if color_type not in ("unchanged", "color"):
+            raise NotImplementedError("BEVLoadMultiViewImageFromFiles(color_type=%r) is not implemented" % (color_type,))
+        self.to_float32, self.color_type, self.backend_args = bool(to_float32), color_type, backend_args
+        self.num_views, self.num_ref_frames = num_views, num_ref_frames
+        self.test_mode, self.set_default_scale = bool(test_mode), bool(set_default_scale)
+        self.defer = bool(defer)
+        if self.defer and self.to_float32:
+            raise ValueError("defer=True leaves the frames undecoded: to_float32 has nothing to convert; use defer=False")
+
+    def _choose_frames(self, results):
+        """The num_ref_frames > 0 branch: picks the reference frames and re-bases their lidar2cam onto the current ego pose."""
+        V, R = self.num_views, self.num_ref_frames
+        num_frames = len(results["img_filename"]) // V - 1
+        if num_frames == 0:  # no previous frame: the current one again
+            choices = np.random.choice(1, R, replace=True)
+        elif num_frames >= R:
+            if self.test_mode:
+                choices = np.arange(num_frames - R, num_frames) + 1
+            else:
+                choices = np.random.choice(num_frames, R, replace=False) + 1
+        elif 0 < num_frames < R:
+            if self.test_mode:
+                choices = np.concatenate([np.arange(num_frames) + 1, np.random.choice(num_frames, R - num_frames, replace=True) + 1])
+            else:
+                choices = np.random.choice(num_frames, R, replace=True) + 1
+        else:
+            raise NotImplementedError
+        choices = np.concatenate([np.array([0], dtype=np.int64), choices])
+        pick = lambda seq: [item for c in choices for item in seq[c * V:(c + 1) * V]]  # noqa: E731
+        results["img_filename"] = pick(results["img_filename"])
+        for key in ("cam2img", "lidar2cam"):
+            if key in results:
+                results[key] = pick(results[key])
+        if "ego2global" in results:
+            results["ego2global"] = [results["ego2global"][c] for c in choices]
+        if "lidar2cam" in results:
+            def padded(m):
+                out = np.eye(4)
+                out[:m.shape[0], :m.shape[1]] = m
+                return out
+            for k in range(1, len(choices)):  # only the previous frames move
+                cur2prev = np.linalg.inv(padded(results["ego2global"][k])).dot(padded(results["ego2global"][0]))
+                for i in range(k * V, (k + 1) * V):
+                    results["lidar2cam"][i] = results["lidar2cam"][i].dot(cur2prev)
+        return choices
+
+    def transform(self, results):
+        if self.num_ref_frames > 0:
+            self._choose_frames(results)
+        filename, cam2img, lidar2cam, cam2lidar, lidar2img = [], [], [], [], []
+        for cam in results["images"].values():
+            filename.append(cam["img_path"])
+            lidar2cam.append(cam["lidar2cam"])
+            l2c = np.array(cam["lidar2cam"]).astype(np.float32)
+            rot, trans = l2c[:3, :3], l2c[:3, 3:4]
+            c2l = np.eye(4)
+            c2l[:3, :3] = rot.T
+            c2l[:3, 3:4] = -1 * np.matmul(rot.T, trans.reshape(3, 1))
+            cam2lidar.append(c2l)
+            c2i = np.eye(4).astype(np.float32)
+            c2i[:3, :3] = np.array(cam["cam2img"]).astype(np.float32)
+            cam2img.append(c2i)
+            lidar2img.append(c2i @ l2c)
+        results["img_path"] = filename
+        results["cam2img"] = np.stack(cam2img, axis=0)
+        results["lidar2cam"] = np.stack(lidar2cam, axis=0)
+        results["cam2lidar"] = np.stack(cam2lidar, axis=0)
+        results["lidar2img"] = np.stack(lidar2img, axis=0)
+        results["ori_cam2img"] = copy.deepcopy(results["cam2img"])
+
+        streams = [np.fromfile(name, dtype=np.uint8) for name in filename]
+        headers = [jpeg.parse(s) for s in streams]
+        unsupported = [h for h in headers if not h.supported]
+        if unsupported:  # the whole sample on the host
+            imgs = [_host_decode(s, jpeg.REASONS.get(unsupported[0].reason, "unsupported")) for s in streams]
+            frames = None
+        elif self.defer:
+            frames = jpeg.JpegFrames.from_bytes(streams)
+            imgs = None
+        else:
+            imgs = [jpeg.torch_jpeg_decode(*jpeg.entropy_decode(s, h)).numpy() for s, h in zip(streams, headers)]
+            frames = None
+        if imgs is not None:
+            shapes = np.stack([img.shape for img in imgs], axis=0)
+            assert shapes.min(0)[-1] == shapes.max(0)[-1]
+            imgs = [_pad_to(img, tuple(shapes.max(0)[:2])) for img in imgs]
+            shape = imgs[0].shape[:2]
+            if self.defer:  # a sample the fused decoder does not take: the ordinary raw block
+                results["img"] = np.stack(imgs, 0)
+            else:
+                results["img"] = [img.astype(np.float32) if self.to_float32 else img for img in imgs]
+        else:
+            shape = frames.shape[1:3]
+            results["img"] = frames
+        results["filename"] = filename
+        results["img_shape"] = results["ori_shape"] = results["pad_shape"] = tuple(int(v) for v in shape)
+        if self.set_default_scale:
+            results["scale_factor"] = 1.0
+        results["img_norm_cfg"] = dict(mean=np.zeros(3, dtype=np.float32), std=np.ones(3, dtype=np.float32), to_rgb=False)
+        results["num_views"] = self.num_views
+        results["num_ref_frames"] = self.num_ref_frames
+        return results
 
     __call__ = transform

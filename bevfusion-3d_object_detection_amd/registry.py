@@ -45,8 +45,8 @@ class Registry:
 MODELS = Registry("models")
 # data pipeline steps (mmdet3d.registry.TRANSFORMS): ImageAug3D and GridMask (image_aug.py) and the LiDAR chain (points_aug.py):
 # BEVFusionGlobalRotScaleTrans, GlobalRotScaleTrans, BEVFusionRandomFlip3D, PointsRangeFilter, ObjectRangeFilter,
-# ObjectNameFilter, PointShuffle; ObjectSample and its DataBaseSampler (object_sample.py); LoadPointsFromFile and
-# LoadPointsFromMultiSweeps (loading.py)
+# ObjectNameFilter, PointShuffle; ObjectSample and its DataBaseSampler (object_sample.py); LoadPointsFromFile,
+# LoadPointsFromMultiSweeps and BEVLoadMultiViewImageFromFiles (loading.py)
 TRANSFORMS = Registry("transforms")
 
 

@@ -911,6 +911,69 @@ int bfhip_query_init_fwd(const float *h, long long h_sb, long long h_sc, long lo
 int bfhip_query_init_bwd(const long long *top_index, const void *d_rows, int B, int K, int Ch, long long HW, int row_dtype,
                          void *d_flat, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * JPEG decode in two halves (csrc/jpeg_host.h, csrc/jpeg.hip): the serial entropy stage on the host, everything after it
+ *   (dequantise, 8x8 inverse DCT, chroma upsampling, YCbCr -> RGB) on the device, bit for bit what libjpeg's default decode
+ *   (accurate integer IDCT, fancy upsampling) gives.
+ *   bfhip_jpeg_parse / bfhip_jpeg_entropy_decode: HOST ONLY -- no HIP call, safe in a loader's worker; they take untrusted
+ *     bytes and neither read outside [bytes, bytes + n) nor write outside [coef, coef + coef_bytes).
+ *   bfhip_jpeg_parse reads the markers up to the first scan.  0 with `supported` set or cleared (reason: BFHIP_JPEG_R_*), or
+ *     BFHIP_E_INVALID for a malformed stream.  The fused path takes baseline sequential (SOF0) 8-bit files of three
+ *     components in one scan, luma sampled 1x1, 2x1, 1x2 or 2x2 and chroma 1x1, 8-bit quantisation tables, no EXIF
+ *     orientation tag.  For a supported stream: block_cols / block_rows per component padded to whole MCUs, quant per
+ *     component in natural (row-major) order, coef_offset in int16 elements, coef_bytes the size of the coefficient buffer.
+ *   bfhip_jpeg_entropy_decode writes, per component at coef_offset, [block_rows, block_cols, 64] int16 coefficients in natural
+ *     order with the DC prediction undone, not dequantised.  Restart intervals, byte stuffing and the file's own Huffman
+ *     tables are handled; a scan that ends early leaves the remaining blocks zero, as libjpeg does.  `header` must be what
+ *     bfhip_jpeg_parse gave for the same bytes; coef_bytes >= header->coef_bytes.  0 or BFHIP_E_INVALID.
+ *   bfhip_jpeg_decode: n_frames frames in TWO launches.  frames_host / frames_dev: the same descriptors in host and in device
+ *     memory; the host copy is validated against coef_elems, planes_bytes and rgb_bytes before anything is launched.
+ *     coef_off: int16 elements from coef_dev (a multiple of 8), the component's [block_rows, block_cols, 64] block.  plane_off:
+ *     bytes from planes_dev (a multiple of 8), the component's uint8 plane [block_rows * 8, block_cols * 8], written by the
+ *     first launch (dequantise + IDCT: 32-bit wrap-around arithmetic, column pass descaled by 11, row pass by 18, + 128,
+ *     clamped) and read by the second (triangle-filter upsampling whose neighbours outside the component's real extent
+ *     ceil(width / hs) x ceil(height / vs) are the nearest real sample; 16-bit fixed-point colour conversion).  rgb_off: bytes
+ *     from rgb_dev of the frame's uint8 [height, width, 3] block; exactly those bytes are written.  hs, vs: luma sampling,
+ *     1 or 2 each; chroma is 1x1.  Frames must not overlap in planes_dev or rgb_dev.  n_frames <= 65535.
+ *     No allocation, no synchronisation; everything runs on `stream`.
+ * --------------------------------------------------------------------------------------- */
+#define BFHIP_JPEG_R_OK 0
+#define BFHIP_JPEG_R_PROGRESSIVE 1
+#define BFHIP_JPEG_R_ARITHMETIC 2
+#define BFHIP_JPEG_R_PRECISION 3        /* not 8 bits per sample */
+#define BFHIP_JPEG_R_COMPONENTS 4       /* not three components */
+#define BFHIP_JPEG_R_MULTI_SCAN 5       /* the first scan does not hold every component */
+#define BFHIP_JPEG_R_QUANT16 6          /* a 16-bit quantisation table */
+#define BFHIP_JPEG_R_SAMPLING 7
+#define BFHIP_JPEG_R_EXIF_ORIENTATION 8
+#define BFHIP_JPEG_R_NOT_BASELINE 9     /* extended sequential, lossless or hierarchical */
+#define BFHIP_JPEG_R_COLOUR_SPACE 10    /* the components are not YCbCr (no JFIF marker and Adobe / the ids say RGB) */
+typedef struct bfhip_jpeg_header {
+  int32_t width, height, ncomp;
+  int32_t supported, reason;
+  int32_t restart_interval;
+  int32_t mcus_x, mcus_y;
+  int32_t hs[3], vs[3];
+  int32_t block_cols[3], block_rows[3];
+  int64_t coef_offset[3];
+  int64_t coef_bytes;
+  uint16_t quant[3][64];
+} bfhip_jpeg_header;
+typedef struct bfhip_jpeg_frame {
+  int64_t coef_off[3];
+  int64_t plane_off[3];
+  int64_t rgb_off;
+  int32_t width, height;
+  int32_t hs, vs;
+  int32_t block_cols[3], block_rows[3];
+  uint16_t quant[3][64];
+} bfhip_jpeg_frame;
+int bfhip_jpeg_parse(const uint8_t *bytes, size_t n, bfhip_jpeg_header *header);
+int bfhip_jpeg_entropy_decode(const uint8_t *bytes, size_t n, const bfhip_jpeg_header *header, int16_t *coef, size_t coef_bytes);
+int bfhip_jpeg_decode(const bfhip_jpeg_frame *frames_host, const bfhip_jpeg_frame *frames_dev, int n_frames,
+                      const int16_t *coef_dev, size_t coef_elems, uint8_t *planes_dev, size_t planes_bytes, uint8_t *rgb_dev,
+                      size_t rgb_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
