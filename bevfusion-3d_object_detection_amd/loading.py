@@ -16,6 +16,9 @@ sweeps' raw rows] -- untouched file contents: the loader's worker does nothing b
 the step into data["points_aug_plan"], in front of ObjectSample's paste and the chain; Det3DDataPreprocessor.process_points runs
 it on the device with the rest of the plan (csrc/points_aug.hip).  Deferral needs use_dim == range(load_dim), 5 <= load_dim <= 8.
 
+LoadAnnotations3D (M3D/datasets/transforms/loading.py:832-1071), the step behind them, moves gt_bboxes_3d / gt_labels_3d /
+attr_labels from `ann_info` to the root of the results; it touches no points.
+
 BEVLoadMultiViewImageFromFiles (BF/loading.py:13-208, keywords of mmdet3d's LoadMultiViewImageFromFiles) is the first step of
 the camera side.  From `images` (per camera img_path, cam2img, lidar2cam) it makes cam2img / lidar2cam / cam2lidar / lidar2img /
 ori_cam2img with the reference's dtypes and operation order -- lidar2cam in float32, cam2lidar a float64 eye(4) filled from the
@@ -131,6 +134,44 @@ class LoadPointsFromMultiSweeps:
             out = out[:, self.use_dim]
         data["points"] = out if was_tensor else out.numpy()
         return data
+
+    __call__ = transform
+
+
+@TRANSFORMS.register_module()
+class LoadAnnotations3D:
+    """The reference's LoadAnnotations3D (M3D/datasets/transforms/loading.py:832-1071) for what the detection pipelines use of
+    it: with_bbox_3d copies ann_info.gt_bboxes_3d to gt_bboxes_3d, with_label_3d ann_info.gt_labels_3d to gt_labels_3d,
+    with_attr_label ann_info.attr_labels to attr_labels.  Boxes that come wrapped (anything with `.tensor`, as the reference's
+    LiDARInstance3DBoxes) are handed on as their float32 tensor, arrays and tensors as they are: what the transforms behind
+    it take (points_aug._unwrap).  Every other with_* flag raises NotImplementedError when set; poly2mask, seg_3d_dtype,
+    seg_offset and dataset_type belong to those branches and are kept; backend_args is accepted and ignored."""
+    _UNSUPPORTED = ("with_mask_3d", "with_seg_3d", "with_bbox", "with_label", "with_mask", "with_seg", "with_bbox_depth",
+                    "with_panoptic_3d")
+
+    def __init__(self, with_bbox_3d=True, with_label_3d=True, with_attr_label=False, with_mask_3d=False, with_seg_3d=False,
+                 with_bbox=False, with_label=False, with_mask=False, with_seg=False, with_bbox_depth=False, with_panoptic_3d=False,
+                 poly2mask=True, seg_3d_dtype="np.int64", seg_offset=None, dataset_type=None, backend_args=None):
+        given = dict(with_mask_3d=with_mask_3d, with_seg_3d=with_seg_3d, with_bbox=with_bbox, with_label=with_label,
+                     with_mask=with_mask, with_seg=with_seg, with_bbox_depth=with_bbox_depth, with_panoptic_3d=with_panoptic_3d)
+        for name in self._UNSUPPORTED:
+            if given[name]:
+                raise NotImplementedError("LoadAnnotations3D(%s=True) is not implemented" % name)
+            setattr(self, name, False)
+        self.with_bbox_3d, self.with_label_3d, self.with_attr_label = bool(with_bbox_3d), bool(with_label_3d), bool(with_attr_label)
+        self.poly2mask, self.seg_3d_dtype, self.seg_offset, self.dataset_type = poly2mask, seg_3d_dtype, seg_offset, dataset_type
+        self.backend_args = backend_args
+
+    def transform(self, results):
+        ann = results["ann_info"]
+        if self.with_bbox_3d:
+            boxes = ann["gt_bboxes_3d"]
+            results["gt_bboxes_3d"] = boxes.tensor if hasattr(boxes, "tensor") else boxes
+        if self.with_label_3d:
+            results["gt_labels_3d"] = ann["gt_labels_3d"]
+        if self.with_attr_label:
+            results["attr_labels"] = ann["attr_labels"]
+        return results
 
     __call__ = transform
 

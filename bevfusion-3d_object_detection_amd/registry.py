@@ -46,7 +46,8 @@ MODELS = Registry("models")
 # data pipeline steps (mmdet3d.registry.TRANSFORMS): ImageAug3D and GridMask (image_aug.py) and the LiDAR chain (points_aug.py):
 # BEVFusionGlobalRotScaleTrans, GlobalRotScaleTrans, BEVFusionRandomFlip3D, PointsRangeFilter, ObjectRangeFilter,
 # ObjectNameFilter, PointShuffle; ObjectSample and its DataBaseSampler (object_sample.py); LoadPointsFromFile,
-# LoadPointsFromMultiSweeps and BEVLoadMultiViewImageFromFiles (loading.py)
+# LoadPointsFromMultiSweeps, LoadAnnotations3D and BEVLoadMultiViewImageFromFiles (loading.py).  gt_database.py builds the
+# database DataBaseSampler reads with the first three of those.
 TRANSFORMS = Registry("transforms")
 
 

@@ -974,6 +974,34 @@ int bfhip_jpeg_decode(const bfhip_jpeg_frame *frames_host, const bfhip_jpeg_fram
                       const int16_t *coef_dev, size_t coef_elems, uint8_t *planes_dev, size_t planes_bytes, uint8_t *rgb_dev,
                       size_t rgb_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Points in rotated boxes, per box (csrc/points_in_boxes.hip): box_np_ops.points_in_rbbox (M3D/structures/ops/box_np_ops.py
+ *   :354-377, 643-677) and the per-box gathers of the ground-truth database builder (tools/dataset_converters/
+ *   create_gt_database.py:257, 296-297), as bevfusion_amd/box_ops.py: torch_points_in_boxes defines them.
+ *   points: float32 [n, C], 4-byte aligned, 3 <= C <= 8, n < 2^31.  planes: float32 [K, 6, 4], per box six inward plane equations
+ *     (n0, n1, n2, d) (bevfusion_amd/points_aug.py: paste_planes); K <= bfhip_points_in_boxes_max_boxes() = 256.  Row i is in box
+ *     j unless ((x n0 + y n1) + z n2) + d >= 0 for one of its planes, every product and sum one float32 operation, never fused;
+ *     a NaN sign therefore leaves the row inside.
+ *   bfhip_points_in_boxes_count (two launches): counts int32 [K], the rows in each box.  member: NULL, or uint64 [n, ceil(K /
+ *     64)], 8-byte aligned: bit j % 64 of word j / 64 of row i is set when row i is in box j (with NULL the words live in the
+ *     workspace).  The workspace, 256-byte aligned, bfhip_points_in_boxes_workspace_bytes(n, K) bytes, also keeps the row
+ *     offsets per (box, workgroup of bfhip_points_in_boxes_block() rows) and must reach the gather unchanged.
+ *   bfhip_points_in_boxes_gather (one launch): out float32 [capacity, C]; the rows of box j, in ascending row index, at rows
+ *     [start_j, start_j + counts_j), start the exclusive prefix sum of counts; a row in two boxes is written once for each.
+ *     centers: NULL, or float32 [K, 3]: columns 0..2 of a row of box j are point - centers[j], one float32 subtraction each; the
+ *     other columns are copied.  total: the sum of counts, which the caller has read; total < 2^31 and capacity >= total, or
+ *     the call is rejected.  n, C, K, counts, member and the workspace as they were given to the count call.
+ *   No allocation, no synchronisation, no atomics: every output is the same bytes on every run.
+ * --------------------------------------------------------------------------------------- */
+int bfhip_points_in_boxes_block(void);
+int bfhip_points_in_boxes_max_boxes(void);
+size_t bfhip_points_in_boxes_workspace_bytes(long long n, int K);
+int bfhip_points_in_boxes_count(const float *points, long long n, int C, const float *planes, int K, int32_t *counts,
+                                uint64_t *member, void *workspace, size_t workspace_bytes, void *stream);
+int bfhip_points_in_boxes_gather(const float *points, long long n, int C, const float *centers, int K, const int32_t *counts,
+                                 const uint64_t *member, long long total, float *out, long long capacity, const void *workspace,
+                                 size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
