@@ -407,6 +407,25 @@ def _lib_dgrad(dy, x, weight, stride, pad, dil):
                                                [True, False, False])[0]
 
 
+class _FixedOrderBiasGrad(torch.autograd.Function):
+    """y -> y, with `bias` attached to the graph behind it: the backward hands dy on untouched and gives `bias` the fixed-order
+    fp32 sum of dy over batch and pixels.  For a library convolution run with the bias detached (Conv2d.forward): forward, data
+    and weight gradient stay the library's own autograd path (autocast and its weight-cast cache included), the library's bias
+    gradient -- whose summation order changes from run to run (198-channel depthnet head: about 15 of 198 elements, up to 4
+    bf16 ulps) -- is not computed at all."""
+
+    @staticmethod
+    def forward(ctx, y, bias):
+        ctx.bias_dtype = bias.dtype
+        ctx.mark_dirty(y)  # y itself is the output (nothing is written): a view could not be modified in place by the next layer
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        db = dy.sum(dim=(0, 2, 3), dtype=torch.float32).to(ctx.bias_dtype) if ctx.needs_input_grad[1] else None
+        return dy, db
+
+
 class _LibConvHipWgradFunction(torch.autograd.Function):
     """Forward and data gradient by the library convolution (MIOpen / CK through torch), weight gradient by csrc/conv2d_wgrad.hip:
     for layers where the library's forward is ahead (ResNet-50's 1x1 and 3x3 convolutions) but its weight gradient brings an
@@ -633,7 +652,8 @@ def lib_conv2d(x, weight, stride, padding, dilation, dgrad_hip=False):
 class Conv2d(nn.Conv2d):
     """nn.Conv2d whose forward runs csrc/conv2d.hip when it can (module docstring)."""
 
-    def hip_eligible(self, x):
+    def _hip_domain(self, x):
+        """A call the HIP kernels are meant for -- bf16 (or bf16 autocast), large enough, plain geometry -- whatever its shape."""
         if not (ENABLED and x.is_cuda and x.dim() == 4 and self.groups == 1 and self.padding_mode == "zeros"
                 and not isinstance(self.padding, str)):
             return False
@@ -645,8 +665,13 @@ class Conv2d(nn.Conv2d):
         if s is None or p is None or d is None:
             return False
         N, Cin, H, W = x.shape
-        if N * H * W < MIN_PIXELS or Cin < MIN_CIN:
+        return N * H * W >= MIN_PIXELS and Cin >= MIN_CIN
+
+    def hip_eligible(self, x):
+        if not self._hip_domain(x):
             return False
+        s, p, d = _one(self.stride), _one(self.padding), _one(self.dilation)
+        N, Cin, H, W = x.shape
         return bool(_lib.load().bfhip_conv2d_supported(N, H, W, Cin, self.out_channels, self.kernel_size[0], self.kernel_size[1],
                                                        s, p, d))
 
@@ -676,6 +701,9 @@ class Conv2d(nn.Conv2d):
                 if partial is not None:
                     y._bfhip_stat_partial = (partial, y.data_ptr(), y._version)
                 return y
+            if self.bias is not None and self.bias.requires_grad and torch.is_grad_enabled() and self._hip_domain(x):
+                # a bf16 layer of the HIP kernels' size range whose shape they do not serve (198 output channels)
+                return _FixedOrderBiasGrad.apply(self._conv_forward(x, self.weight, self.bias.detach()), self.bias)
             return super().forward(x)
         emit = self.training and self.bias is None and torch.is_grad_enabled()
         y, partial = conv2d(x, self.weight, self.bias, _one(self.stride), _one(self.padding), _one(self.dilation), emit)

@@ -410,7 +410,7 @@ BFHIP_EXPORT int bfhip_attn_fwd(const void *Q, const void *K, const void *V, int
   BFHIP_REQUIRE(make_dims(B, H, Lq, Lk, scale, dropout_p, seed, seed_dev, dm) == 0, "attn_fwd: unsupported sizes B=%d H=%d Lq=%d Lk=%d (Lq <= 512, head dim 16)", B, H, Lq, Lk);
   BFHIP_REQUIRE(Q && K && V && O && lse, "attn_fwd: null pointer");
   BFHIP_REQUIRE(((uintptr_t)Q % 8) == 0 && ((uintptr_t)K % 8) == 0 && ((uintptr_t)V % 8) == 0, "attn_fwd: tensors must be 8-byte aligned");
-  if (!workspace || workspace_bytes < bfhip_attn_workspace_bytes(B, H, Lq, Lk)) { set_error("attn_fwd: workspace too small"); return BFHIP_E_WORKSPACE; }
+  BFHIP_REQUIRE_WORKSPACE(workspace, workspace_bytes, bfhip_attn_workspace_bytes(B, H, Lq, Lk), "attn_fwd");
   float2 *lpart = (float2 *)workspace;
   float *opart = (float *)((char *)workspace + align_up((size_t)B * H * dm.nchunk * Lq * sizeof(float2), 256));
   dim3 grid(dm.nchunk, B * H, ceil_div(Lq, kMaxQT * 16));  // z: blocks of 256 queries
@@ -432,7 +432,7 @@ BFHIP_EXPORT int bfhip_attn_bwd(const void *Q, const void *K, const void *V, con
   Dims dm;
   BFHIP_REQUIRE(make_dims(B, H, Lq, Lk, scale, dropout_p, seed, seed_dev, dm) == 0, "attn_bwd: unsupported sizes");
   BFHIP_REQUIRE(Q && K && V && O && dO && lse && dQ && dK && dV, "attn_bwd: null pointer");
-  if (!workspace || workspace_bytes < bfhip_attn_workspace_bytes(B, H, Lq, Lk)) { set_error("attn_bwd: workspace too small"); return BFHIP_E_WORKSPACE; }
+  BFHIP_REQUIRE_WORKSPACE(workspace, workspace_bytes, bfhip_attn_workspace_bytes(B, H, Lq, Lk), "attn_bwd");
   float *dqpart = (float *)((char *)workspace + align_up((size_t)B * H * dm.nchunk * Lq * sizeof(float2), 256));
   dim3 grid(dm.nchunk, B * H);
 #define BFHIP_ATTN_BWD(DROP, NQT)                                                                                         \

@@ -203,7 +203,7 @@ BFHIP_EXPORT int bfhip_bn1d_fwd(const float *x, const float *residual, const flo
   BFHIP_REQUIRE(x && gamma && beta && stats && y, "bn1d_fwd: null pointer");
   BFHIP_REQUIRE(((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 16) == 0 && (!residual || ((uintptr_t)residual % 16) == 0),
                 "bn1d_fwd: tensors must be 16-byte aligned");
-  if (workspace_bytes < bfhip_bn1d_workspace_bytes(N, C) || !workspace) { set_error("bn1d_fwd: workspace too small"); return BFHIP_E_WORKSPACE; }
+  BFHIP_REQUIRE_WORKSPACE(workspace, workspace_bytes, bfhip_bn1d_workspace_bytes(N, C), "bn1d_fwd");
   float *partial = (float *)workspace;
   int nblk = ceil_div(N, kSlab);
   hipLaunchKernelGGL(bn_stats_kernel, dim3(nblk), dim3(256), 0, stream, x, N, C, partial);
@@ -222,7 +222,7 @@ BFHIP_EXPORT int bfhip_bn1d_bwd(const float *dy, const float *y, const float *x,
   hipStream_t stream = (hipStream_t)stream_;
   BFHIP_REQUIRE(shape_ok(N, C), "bn1d_bwd: needs N > 0 and C in {4,8,16,32,64,128,256} (N=%d C=%d)", N, C);
   BFHIP_REQUIRE(dy && y && x && stats && gamma && dx && dgb, "bn1d_bwd: null pointer");
-  if (workspace_bytes < bfhip_bn1d_workspace_bytes(N, C) || !workspace) { set_error("bn1d_bwd: workspace too small"); return BFHIP_E_WORKSPACE; }
+  BFHIP_REQUIRE_WORKSPACE(workspace, workspace_bytes, bfhip_bn1d_workspace_bytes(N, C), "bn1d_bwd");
   float *partial = (float *)workspace;
   int nblk = ceil_div(N, kSlab);
   hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(nblk), dim3(256), 0, stream, dy, y, x, stats, N, C, relu, partial);

@@ -622,7 +622,7 @@ BFHIP_EXPORT int bfhip_colsum(const void *x, long long M, int C, int dtype, floa
   hipStream_t s = (hipStream_t)stream_;
   BFHIP_REQUIRE(bfhip_bn2d_supported(M, C, dtype), "colsum: unsupported shape M=%lld C=%d dtype=%d", M, C, dtype);
   BFHIP_REQUIRE(x && out && ((uintptr_t)x % 16) == 0, "colsum: null or misaligned pointer");
-  if (!workspace || workspace_bytes < bfhip_bn2d_workspace_bytes(M, C, dtype)) { set_error("colsum: workspace too small"); return BFHIP_E_WORKSPACE; }
+  BFHIP_REQUIRE_WORKSPACE(workspace, workspace_bytes, bfhip_bn2d_workspace_bytes(M, C, dtype), "colsum");
   Plan pl;
   plan_bytes(M, C, dtype, &pl, workspace);
   Tree tr{nullptr, pl.gp, pl.nblk, pl.ng};
@@ -644,7 +644,7 @@ BFHIP_EXPORT int bfhip_bn2d_fwd(const void *x, const void *residual, const float
   BFHIP_REQUIRE(x && gamma && beta && stats && y, "bn2d_fwd: null pointer");
   BFHIP_REQUIRE(((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 16) == 0 && ((uintptr_t)residual % 16) == 0,
                 "bn2d_fwd: tensors must be 16-byte aligned");
-  if (!workspace || workspace_bytes < bfhip_bn2d_workspace_bytes(M, C, dtype)) { set_error("bn2d_fwd: workspace too small"); return BFHIP_E_WORKSPACE; }
+  BFHIP_REQUIRE_WORKSPACE(workspace, workspace_bytes, bfhip_bn2d_workspace_bytes(M, C, dtype), "bn2d_fwd");
   Plan pl;
   plan_bytes(M, C, dtype, &pl, workspace);
   int *cnt = fold_enabled() ? arrival_counters(s) : nullptr;
@@ -717,7 +717,7 @@ static int bn2d_bwd_impl(const void *dy, const void *x, const void *y, const uns
   BFHIP_REQUIRE(dy && x && stats && gamma && dx && dgb, "bn2d_bwd: null pointer");
   BFHIP_REQUIRE(((uintptr_t)dy % 16) == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)dx % 16) == 0 &&
                     ((uintptr_t)y % 16) == 0 && ((uintptr_t)dres % 16) == 0, "bn2d_bwd: tensors must be 16-byte aligned");
-  if (!workspace || workspace_bytes < bfhip_bn2d_workspace_bytes(M, C, dtype)) { set_error("bn2d_bwd: workspace too small"); return BFHIP_E_WORKSPACE; }
+  BFHIP_REQUIRE_WORKSPACE(workspace, workspace_bytes, bfhip_bn2d_workspace_bytes(M, C, dtype), "bn2d_bwd");
   Plan pl;
   plan_bytes(M, C, dtype, &pl, workspace);
   int *cnt = fold_enabled() ? arrival_counters(s) : nullptr;

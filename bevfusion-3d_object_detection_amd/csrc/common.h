@@ -107,3 +107,9 @@ int spconv_wgrad_tr(const void *in, const void *dout, const int32_t *pairs, int 
       return BFHIP_E_INVALID;                   \
     }                                           \
   } while (0)
+
+// the caller-provided workspace `ptr` of `have` bytes must hold `need`; name = string literal, the op's name in the message
+#define BFHIP_REQUIRE_WORKSPACE(ptr, have, need, name)                                                           \
+  do {                                                                                                           \
+    if ((have) < (need) || !(ptr)) { bfhip::set_error(name ": workspace too small"); return BFHIP_E_WORKSPACE; } \
+  } while (0)

@@ -178,7 +178,7 @@ BFHIP_EXPORT int bfhip_rasterise_depth(const float *points, int n, int f, const 
   BFHIP_REQUIRE(depth && inv_rot && aug_trans && lidar2image && img_aug, "rasterise_depth: null pointer");
   BFHIP_REQUIRE(!counts || (fH > 0 && fW > 0 && D > 0 && iH % fH == 0 && iW % fW == 0 && dbound_host),
                 "rasterise_depth: histogram needs fH | iH, fW | iW and dbound");
-  if (workspace_bytes < bfhip_rasterise_depth_workspace_bytes(ncam, iH, iW) || !workspace) { set_error("rasterise_depth: workspace too small"); return BFHIP_E_WORKSPACE; }
+  BFHIP_REQUIRE_WORKSPACE(workspace, workspace_bytes, bfhip_rasterise_depth_workspace_bytes(ncam, iH, iW), "rasterise_depth");
   unsigned long long *winner = (unsigned long long *)workspace;
   long long npix = (long long)ncam * iH * iW;
   ProfScope ps;
@@ -209,7 +209,7 @@ BFHIP_EXPORT int bfhip_depth_lift_bwd(const void *dy, const void *d, long long M
   hipStream_t stream = (hipStream_t)stream_;
   BFHIP_REQUIRE(dy && d && out && M > 0, "depth_lift_bwd: bad arguments");
   BFHIP_REQUIRE(((uintptr_t)dy % 16) == 0 && ((uintptr_t)d % 2) == 0, "depth_lift_bwd: misaligned tensor");
-  if (!workspace || workspace_bytes < bfhip_depth_lift_bwd_workspace_bytes()) { set_error("depth_lift_bwd: workspace too small"); return BFHIP_E_WORKSPACE; }
+  BFHIP_REQUIRE_WORKSPACE(workspace, workspace_bytes, bfhip_depth_lift_bwd_workspace_bytes(), "depth_lift_bwd");
   const int nblk = (int)(M < (long long)kLiftBlocks * 256 ? ceil_div(M, 256) : kLiftBlocks);
   hipLaunchKernelGGL(depth_lift_bwd_kernel, dim3(nblk), dim3(256), 0, stream, (const uint4 *)dy, (const unsigned short *)d, M,
                      (float *)workspace);

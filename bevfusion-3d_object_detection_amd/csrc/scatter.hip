@@ -235,7 +235,7 @@ BFHIP_EXPORT int bfhip_dynamic_scatter_fwd(const float *feats, const int32_t *co
   if (hipMemsetAsync(counts_dev, 0, 3 * sizeof(int), stream) != hipSuccess) return check_launch("dynamic_scatter memset");
   if (N == 0) return BFHIP_OK;
   BFHIP_REQUIRE(feats && coors && voxel_feats && voxel_coors && point2voxel && voxel_count, "dynamic_scatter_fwd: null pointer");
-  if (workspace_bytes < bfhip_dynamic_scatter_workspace_bytes(N) || !workspace) { set_error("dynamic_scatter_fwd: workspace too small"); return BFHIP_E_WORKSPACE; }
+  BFHIP_REQUIRE_WORKSPACE(workspace, workspace_bytes, bfhip_dynamic_scatter_workspace_bytes(N), "dynamic_scatter_fwd");
   Workspace ws(workspace, workspace_bytes);
   unsigned long long *keys_in = ws.take<unsigned long long>(N), *keys = ws.take<unsigned long long>(N);
   unsigned *vals_in = ws.take<unsigned>(N), *sorted_idx = ws.take<unsigned>(N);
@@ -287,7 +287,7 @@ BFHIP_EXPORT int bfhip_dynamic_scatter_bwd(float *grad_feats, const float *grad_
                        point2voxel, voxel_count, total, C, reduce_type == BFHIP_REDUCE_MEAN);
   } else {
     BFHIP_REQUIRE(feats && voxel_feats, "dynamic_scatter_bwd: null pointer");
-    if (workspace_bytes < bfhip_dynamic_scatter_bwd_workspace_bytes(M, C) || !workspace) { set_error("dynamic_scatter_bwd: workspace too small"); return BFHIP_E_WORKSPACE; }
+    BFHIP_REQUIRE_WORKSPACE(workspace, workspace_bytes, bfhip_dynamic_scatter_bwd_workspace_bytes(M, C), "dynamic_scatter_bwd");
     int *reduce_from = (int *)workspace;
     hipMemsetAsync(grad_feats, 0, (size_t)N * C * sizeof(float), stream);
     (void)hipMemsetAsync(reduce_from, 0x7f, (size_t)M * C * sizeof(int), stream);

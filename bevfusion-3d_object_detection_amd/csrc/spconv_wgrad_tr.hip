@@ -4,7 +4,7 @@
 // (offset k = q*8 / Cin, channels q*8 % Cin ..+8), its source row is pairs[k][row] (-1: no neighbour -> zero piece).  The
 // pair index of the NEXT 64-row step is loaded while the current step computes, so the index -> row chain costs one
 // round trip per step, not two.  bf16 features in, fp32 accumulate: 16x the matrix rate of the fp32-MFMA kernel in
-// spconv.hip, which stays for fp32 features.
+// spconv_wgrad.hip, which stays for fp32 features.
 #include "wgrad_tr.h"
 
 namespace bfhip {
@@ -109,7 +109,7 @@ SpWgradGeom sp_wgrad_geom(int KV, int Cin, int Cout, int ld, int n_rows) {
 }
 }  // namespace
 
-// ---- internal entry points for spconv.hip (declared in common.h)
+// ---- internal entry points for spconv_wgrad.hip (declared in common.h)
 size_t spconv_wgrad_tr_workspace_bytes(int KV, int Cin, int Cout, int n_rows) {
   return align_up((size_t)sp_wgrad_geom(KV, Cin, Cout, 0, n_rows > 0 ? n_rows : 1).splits * Cout * KV * Cin * sizeof(float), 256);
 }

@@ -131,7 +131,7 @@ BFHIP_EXPORT int bfhip_xty(const void *X, const void *Y, long long K, int M, int
   hipStream_t s = (hipStream_t)stream_;
   BFHIP_REQUIRE(X && Y && out && K > 0 && M > 0 && N > 0 && (dtype == 0 || dtype == 1), "xty: bad arguments");
   BFHIP_REQUIRE((long long)M * N < (1LL << 31), "xty: output too large");
-  if (!workspace || workspace_bytes < bfhip_xty_workspace_bytes(K, M, N)) { set_error("xty: workspace too small"); return BFHIP_E_WORKSPACE; }
+  BFHIP_REQUIRE_WORKSPACE(workspace, workspace_bytes, bfhip_xty_workspace_bytes(K, M, N), "xty");
   const int GI = (M + 63) / 64, GJ = (N + 63) / 64;
   const int S = pick_splits(K, GI, GJ);
   float *partial = (float *)workspace;

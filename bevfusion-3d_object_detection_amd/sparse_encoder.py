@@ -1,7 +1,7 @@
 """Host mirror of the LiDAR middle encoder: `BEVFusionSparseEncoder` (BF/sparse_encoder.py:12-156),
 its layer factory `make_encoder_layers` (mmdet3d/models/middle_encoders/sparse_encoder.py:165-241),
 `SparseBasicBlock` and `make_sparse_convmodule` (mmdet3d/models/layers/sparse_block.py:94-224).
-Conv arithmetic: csrc/spconv.hip via spconv.py; BatchNorm1d / ReLU on the [N, C] feature matrix are torch.
+Conv arithmetic: csrc/spconv*.hip and csrc/sparse_bev.hip via spconv.py; BatchNorm1d / ReLU on the [N, C] feature matrix are torch.
 """
 import os
 from typing import Optional, Tuple, Union

@@ -3,8 +3,9 @@
 and the container types it imports from spconv.pytorch (`SparseConvTensor`, `SparseModule`,
 `SparseSequential`; mmdet3d/models/layers/sparse_block.py:11-14, BF/sparse_encoder.py:133).
 
-The arithmetic runs in csrc/spconv.hip.  API surface kept from traveller59/spconv 2.x as the
-reference uses it: `SparseConvTensor(features, indices, spatial_shape, batch_size)` with
+The arithmetic runs in csrc/: spconv_rulebook.hip (rulebooks), spconv.hip (forward / data gradient),
+spconv_wgrad.hip and spconv_wgrad_tr.hip (weight gradient), sparse_bev.hip (dense BEV map).
+API surface kept from traveller59/spconv 2.x as the reference uses it: `SparseConvTensor(features, indices, spatial_shape, batch_size)` with
 `.features .indices .spatial_shape .batch_size .indice_dict .replace_feature() .dense()
 .find_indice_pair() .shadow_copy()`; convs take (in_channels, out_channels, kernel_size,
 stride=, padding=, dilation=, bias=, indice_key=); weight layout (out, k0, k1, k2, in).

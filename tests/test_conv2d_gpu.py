@@ -650,3 +650,43 @@ def test_fp32_convolution_by_three_bf16_products(dev):
             assert _l2(conv(xg).detach().cpu(), ref.detach()) < 1e-5
     finally:
         c2.FP32_SPLIT = old
+
+
+def test_library_conv_bias_grad_is_fixed_order(dev):
+    """A biased bf16 layer that the HIP kernels do not serve (the depthnet head: 1x1, 198 output channels, at the benchmark's
+    size) runs the library's convolution with the bias detached; conv2d._FixedOrderBiasGrad supplies the bias gradient.
+    Forward bits, data gradient and weight gradient are nn.Conv2d's; the bias gradient is the fp32 sum of dy -- within
+    1e-5 * sum|dy| of the fp64 sum (an fp32 tree sum of 67 584 terms: ~17 levels x 2^-24; the library's own bias gradient is
+    off by bf16 ulps, 4e-3 of an element) -- and repeats bit for bit."""
+    torch.manual_seed(0)
+    N, Cin, Cout, H, W = 24, 256, 198, 32, 88
+    conv = Conv2d(Cin, Cout, 1).to(dev).train()
+    ref = torch.nn.Conv2d(Cin, Cout, 1).to(dev).train()
+    ref.load_state_dict(conv.state_dict())
+    x = torch.randn(N, Cin, H, W, device=dev).to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
+    g = torch.randn(N, Cout, H, W, device=dev).to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
+    runs = []
+    for _ in range(3):
+        conv.zero_grad()
+        xi = x.clone().requires_grad_(True)
+        with torch.autocast("cuda", dtype=torch.bfloat16):
+            assert conv._hip_domain(xi) and not conv.hip_eligible(xi)
+            y = conv(xi)
+        y.backward(g)
+        runs.append((y.detach(), xi.grad, conv.weight.grad.clone(), conv.bias.grad.clone()))
+    xr = x.clone().requires_grad_(True)
+    with torch.autocast("cuda", dtype=torch.bfloat16):
+        yr = ref(xr)
+    yr.backward(g)
+    y, dx, dw, db = runs[0]
+    assert y.dtype == torch.bfloat16 and torch.equal(y, yr.detach())
+    assert torch.allclose(dx.float(), xr.grad.float(), rtol=2 ** -7, atol=2 ** -7 * float(xr.grad.abs().max()))
+    assert float((dw - ref.weight.grad).abs().max()) <= 1e-2 * float(ref.weight.grad.abs().max())
+    assert db.dtype == torch.float32 and db.shape == (Cout,)
+    want = g.double().sum(dim=(0, 2, 3))
+    bound = 1e-5 * g.double().abs().sum(dim=(0, 2, 3))
+    assert bool(((db.double() - want).abs() <= bound).all()), float(((db.double() - want).abs() / bound).max())
+    for r in runs[1:]:
+        assert torch.equal(r[3], db) and torch.equal(r[0], y)
+    # a layer without a bias, or outside the HIP kernels' domain (fp32 without autocast), keeps nn.Conv2d's own path
+    assert not conv._hip_domain(x.float())

@@ -1,4 +1,5 @@
-"""GPU parity: csrc/spconv.hip (rulebooks, gather-GEMM, dgrad, wgrad, dense) vs the oracle.
+"""GPU parity: csrc/spconv_rulebook.hip (rulebooks), spconv.hip (gather-GEMM, dgrad), spconv_wgrad.hip (wgrad) and
+sparse_bev.hip (dense) vs the oracle.
 Rulebooks bit-exact (indices); features within 1e-3 rel (fp32 MFMA vs fp64-accumulated oracle)."""
 import numpy as np
 import pytest
@@ -561,6 +562,73 @@ def test_wgrad_abi_geometries_vs_fp64(dev, cin, cout, kv, n_rows, use_perm):
         lib.bfhip_spconv_wgrad(_lib.ptr(tx), _lib.ptr(tg), _lib.ptr(tp), ld, kv, n_rows, cin, cout, _lib.ptr(tperm), _lib.ptr(dw2),
                                io16, _lib.ptr(ws), wsb, _lib.stream_of(tx))
         assert torch.equal(dw, dw2)
+
+
+def _gemm_reference(x, w, pairs, n_rows, transpose, flip):
+    """out[n] = sum over k with pairs[k][n] >= 0 of x[pairs[k][n]] @ M_k in torch fp64 on the CPU; M_k[ci][co] = w[co][k][ci]
+    forward, M_k[co][ci] = w[co][KV-1-k if flip else k][ci] transposed."""
+    kv = pairs.shape[0]
+    xd = x.double()
+    out = torch.zeros(n_rows, w.shape[2] if transpose else w.shape[0], dtype=torch.float64)
+    for k in range(kv):
+        m = w[:, kv - 1 - k if (transpose and flip) else k, :].double()
+        p = torch.from_numpy(pairs[k, :n_rows].astype(np.int64))
+        out += (xd[p.clamp(min=0)] * (p >= 0).unsqueeze(1)) @ (m if transpose else m.t())
+    return out.numpy()
+
+
+_ROW_TILE_CHANNELS = [(16, 16), (64, 32), (16, 128)]   # NT = 1 | 2 | 8; on the bf16 entry: classic, pipelined, classic kernel
+ROW_TILE_CASES = [(n, ci, co, 0, 0, False) for n in (65553, 131089, 262161) for ci, co in _ROW_TILE_CHANNELS] + [
+    (65553, 64, 32, 1, 1, False),   # data gradient of a SubM layer: transposed, flipped offsets
+    (65553, 64, 32, 0, 0, True)]    # mask-sorted form: random row order + the table's row masks
+
+
+@pytest.mark.parametrize("n_rows,kdim,ndim,transpose,flip,use_perm", ROW_TILE_CASES,
+                         ids=lambda v: str(int(v)) if not isinstance(v, bool) else ("perm" if v else "id"))
+def test_gemm_row_tile_variants_vs_fp64(dev, n_rows, kdim, ndim, transpose, flip, use_perm):
+    """The R = 2 and R = 4 row-tile instantiations of the three gather-GEMM kernels (every other parity case has 6 000 rows,
+    R = 1), through spconv._gemm on a synthetic pair table.  All row counts end on a partial 16-row tile.
+      65 553 rows: bf16 entry R = 2 (threshold 65 536), fp32 entry R = 1
+      131 089    : fp32 entry R = 2 (threshold 131 072)
+      262 161    : R = 4 (threshold 262 144); the fp32 entry caps NT = 8 at R = 2
+    KV = 3 offsets: one pairs every row, one about half, one about 5 %; 4 096 source rows; ld = n_rows + 3."""
+    from bevfusion_amd import spconv as sp
+    kv, n_src = 3, 4096
+    rs = np.random.RandomState(n_rows % 9973 + kdim * 131 + ndim * 7 + transpose)
+    pairs = np.full((kv, n_rows + 3), -1, np.int32)
+    for k, density in enumerate((1.0, 0.5, 0.05)):
+        m = rs.rand(n_rows) < density
+        pairs[k, :n_rows][m] = rs.randint(0, n_src, int(m.sum()))
+    assert pairs.min() >= -1 and pairs.max() < n_src     # the kernels trust the table
+    cin, cout = (ndim, kdim) if transpose else (kdim, ndim)
+    x = torch.from_numpy(rs.randn(n_src, kdim).astype(np.float32))
+    w = torch.from_numpy((rs.randn(cout, kv, cin) / np.sqrt(kv * kdim)).astype(np.float32))
+    perm = row_mask = None
+    if use_perm:
+        perm = torch.from_numpy(rs.permutation(n_rows).astype(np.int32)).to(dev)
+        bits = (pairs[:, :n_rows] >= 0).astype(np.uint32) << np.arange(kv, dtype=np.uint32)[:, None]
+        row_mask = torch.from_numpy(np.bitwise_or.reduce(bits, axis=0).astype(np.int32)).to(dev)
+    tp, tw = torch.from_numpy(pairs).to(dev), w.to(dev)
+    want = _gemm_reference(x, w, pairs, n_rows, transpose, flip)
+    want16 = _gemm_reference(x.to(torch.bfloat16).float(), w, pairs, n_rows, transpose, flip)   # from the bf16-rounded inputs
+
+    def run(bf16, io16):
+        tx = x.to(dev).to(torch.bfloat16) if io16 else x.to(dev)
+        out = sp._gemm(tx, tw, tp, n_rows, transpose, flip, perm, row_mask, bf16=bf16, io16=io16)
+        assert out.shape == (n_rows, ndim) and out.dtype == (torch.bfloat16 if io16 else torch.float32)
+        got = out.float().cpu().numpy()
+        assert np.isfinite(got).all()
+        return got
+
+    err = rel_err(run(False, False), want)
+    print("fp32 entry", err)
+    assert err < TOL, err
+    err = rel_err(run(True, False), want)
+    print("bf16 entry, fp32 storage", err)
+    assert 1e-6 < err < 1e-2, err     # really the bf16 path, inside the bf16 budget
+    err = rel_err(run(True, True), want16)
+    print("bf16 entry, bf16 storage", err)
+    assert 1e-6 < err < 1e-2, err
 
 
 def test_sort_rows_is_region_major_mask_sort(dev, sorted_rows):

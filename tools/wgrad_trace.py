@@ -32,7 +32,7 @@ def trace(C, N, pair_fwd, n_pairs, label):
     occ = int(os.environ["BFHIP_WGRAD_BLOCKS_PER_CU"])   # set it: the library's own choice is not visible from here
     P = occ * torch.cuda.get_device_properties(0).multi_processor_count
     T, Ut = 27 * GI * GJ, (N + 63) // 64
-    NR = (4 if GI * GJ == 4 else 8) if Ut >= 64 else 1       # the library's rule (spconv.hip, bfhip_spconv_wgrad)
+    NR = (4 if GI * GJ == 4 else 8) if Ut >= 64 else 1       # the library's rule (spconv_wgrad.hip, bfhip_spconv_wgrad)
     Ur = -(-Ut // NR)
     P = min(P, NR * T * Ur)
     nwaves, S = P * 4, -(-NR * T * Ur // P)
