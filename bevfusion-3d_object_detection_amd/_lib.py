@@ -176,6 +176,15 @@ SIGNATURES = {
     "bfhip_points_in_boxes_count": (_c_int, [_c_vp, ctypes.c_longlong, _c_int, _c_vp, _c_int, _c_vp, _c_vp, _c_vp, _c_sz, _c_vp]),
     "bfhip_points_in_boxes_gather": (_c_int, [_c_vp, ctypes.c_longlong, _c_int, _c_vp, _c_int, _c_vp, _c_vp, ctypes.c_longlong,
                                               _c_vp, ctypes.c_longlong, _c_vp, _c_sz, _c_vp]),
+    "bfhip_detection_eval_max_preds": (_c_int, []),
+    "bfhip_detection_eval_max_gt": (_c_int, []),
+    "bfhip_detection_eval_max_thresholds": (_c_int, []),
+    "bfhip_detection_eval_max_classes": (_c_int, []),
+    "bfhip_detection_match": (_c_int, [_c_vp] * 4 + [ctypes.c_longlong] + [_c_vp] * 3 + [ctypes.c_longlong, _c_int, _c_int, _c_vp,
+                                       _c_int, _c_int, ctypes.c_uint64, ctypes.c_uint64, _c_vp, _c_vp, _c_vp]),
+    "bfhip_detection_curves_workspace_bytes": (_c_sz, [ctypes.c_longlong, _c_int]),
+    "bfhip_detection_curves": (_c_int, [_c_vp] * 5 + [ctypes.c_longlong, _c_int, _c_int, _c_int, _c_vp, _c_vp, ctypes.c_double,
+                                        _c_int, ctypes.c_uint64] + [_c_vp] * 6 + [_c_vp, _c_sz, _c_vp]),
 }
 
 

@@ -49,6 +49,9 @@ MODELS = Registry("models")
 # LoadPointsFromMultiSweeps, LoadAnnotations3D and BEVLoadMultiViewImageFromFiles (loading.py).  gt_database.py builds the
 # database DataBaseSampler reads with the first three of those.
 TRANSFORMS = Registry("transforms")
+# evaluators (mmdet3d.registry.METRICS): NuScenesCustomMetric (evaluation.py), the `val_evaluator` of the reference's custom-data
+# configs -- the nuScenes detection protocol (matching, PR curves, mAP, the TP errors, NDS) on what predict() returns.
+METRICS = Registry("metrics")
 
 
 def register(target):

@@ -1002,6 +1002,44 @@ int bfhip_points_in_boxes_gather(const float *points, long long n, int C, const 
                                  const uint64_t *member, long long total, float *out, long long capacity, const void *workspace,
                                  size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * nuScenes detection protocol (csrc/detection_eval.hip): greedy centre-distance matching, PR curves, AP and TP errors, as
+ *   bevfusion_amd/evaluation.py: numpy_detection_eval defines them (the reference's NuScenesCustomMetric, projects/BEVFusion/
+ *   evaluation/, runs the nuScenes devkit's accumulate / calc_ap / calc_tp on the host).  Two launches for any number of samples.
+ *   Boxes are float32 rows of 9: x, y, z, dx, dy, dz, yaw, vx, vy.  pred_off / gt_off: int32 [n_samples + 1], the first row of
+ *     each sample; at most bfhip_detection_eval_max_preds() = 512 predictions per sample.  pred_cls / gt_cls: int32, the index into
+ *     the evaluated classes, or -1 (ignored); n_classes <= bfhip_detection_eval_max_classes() = 64; at most
+ *     bfhip_detection_eval_max_gt() = 1024 GT boxes per (sample, class) -- further ones are not seen; the caller checks.
+ *   bfhip_detection_match (one launch): per (sample, class, threshold) the class's predictions of the sample, by (score descending,
+ *     row descending), each take the nearest not yet taken GT of the class in the sample (float64 sqrt(dx dx + dy dy) of the x, y
+ *     centres; equal distance: the lower row) when its distance is < the threshold.  dist_ths: HOST float64 [n_ths], n_ths <=
+ *     bfhip_detection_eval_max_thresholds() = 8.  match: int32 [n_ths, n_pred], the GT row or -1, written for every prediction with
+ *     a class (the caller presets the others).  pred_err: float64 [n_pred, 5], the errors (translation, scale, orientation,
+ *     velocity, attribute) of the match at threshold tp_index, NaN where unmatched.  Bit c of half_period_mask: class c's
+ *     orientation error has period pi, not 2 pi; bit c of attr_empty_mask: its attribute error is NaN, not 0.
+ *   bfhip_detection_curves (one launch): order: int32 [n_pred], the prediction rows by (class ascending, score descending, row
+ *     descending), the ignored class last; cls_off: int32 [n_classes + 1], each class's first position in it.  npos: int32
+ *     [n_classes], the GT boxes of each class.  levels: float64 [101], the recall levels.  Out: precision and confidence float64
+ *     [n_classes, n_ths, 101], err_curves float64 [n_classes, 5, 101] (at tp_index), ap float64 [n_classes, n_ths], tp_err float64
+ *     [n_classes, 5], max_recall_ind int32 [n_classes].  The workspace, 256-byte aligned, has
+ *     bfhip_detection_curves_workspace_bytes(n_pred, n_ths) bytes.
+ *   No allocation, no synchronisation, no atomics: the same bytes on every run.  All pointers but dist_ths are device pointers.
+ * --------------------------------------------------------------------------------------- */
+int bfhip_detection_eval_max_preds(void);
+int bfhip_detection_eval_max_gt(void);
+int bfhip_detection_eval_max_thresholds(void);
+int bfhip_detection_eval_max_classes(void);
+int bfhip_detection_match(const float *pred, const float *score, const int32_t *pred_cls, const int32_t *pred_off, long long n_pred,
+                          const float *gt, const int32_t *gt_cls, const int32_t *gt_off, long long n_gt, int n_samples,
+                          int n_classes, const double *dist_ths, int n_ths, int tp_index, uint64_t half_period_mask,
+                          uint64_t attr_empty_mask, int32_t *match, double *pred_err, void *stream);
+size_t bfhip_detection_curves_workspace_bytes(long long n_pred, int n_ths);
+int bfhip_detection_curves(const float *score, const int32_t *order, const int32_t *cls_off, const int32_t *match,
+                           const double *pred_err, long long n_pred, int n_classes, int n_ths, int tp_index, const int32_t *npos,
+                           const double *levels, double min_precision, int first_level, uint64_t attr_empty_mask,
+                           double *precision, double *confidence, double *err_curves, double *ap, double *tp_err,
+                           int32_t *max_recall_ind, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
