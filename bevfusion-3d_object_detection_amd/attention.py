@@ -17,15 +17,21 @@ _WS = {}
 _calls = itertools.count(1)
 
 
-def _eligible(q, k, v, num_heads):
+MAX_DROPOUT_WEIGHTS = 1 << 32
+
+
+def _eligible(q, k, v, num_heads, dropout_p=0.0):
+    """dropout_p > 0: the kernels hash a 32-bit element index, so B*H*Lq*Lk may not exceed 2^32 (make_dims in csrc/attn.hip
+    refuses it: masks would repeat); such a call takes the library path."""
     return (ENABLED and q.is_cuda and q.dtype == k.dtype == v.dtype == torch.bfloat16 and q.dim() == 3
             and q.shape[2] == num_heads * 16 and k.shape[1] >= MIN_KEYS and k.shape == v.shape
-            and q.shape[0] == k.shape[0])
+            and q.shape[0] == k.shape[0]
+            and (dropout_p <= 0.0 or q.shape[0] * num_heads * q.shape[1] * k.shape[1] <= MAX_DROPOUT_WEIGHTS))
 
 
-def supported(q, k, v, num_heads):
+def supported(q, k, v, num_heads, dropout_p=0.0):
     """The single-block path: every query of a (batch, head) in one workgroup, at most 256 queries."""
-    return _eligible(q, k, v, num_heads) and q.shape[1] <= 256
+    return _eligible(q, k, v, num_heads, dropout_p) and q.shape[1] <= 256
 
 
 def max_queries():
@@ -33,10 +39,10 @@ def max_queries():
     return int(_lib.load().bfhip_attn_max_queries())
 
 
-def supported_wide(q, k, v, num_heads):
+def supported_wide(q, k, v, num_heads, dropout_p=0.0):
     """The same conditions for 256 < Lq <= max_queries() (the custom_data head's 500 proposals): query-block grid axis in the
     forward, 32 query tiles per key tile in the backward."""
-    return WIDE and _eligible(q, k, v, num_heads) and 256 < q.shape[1] <= max_queries()
+    return WIDE and _eligible(q, k, v, num_heads, dropout_p) and 256 < q.shape[1] <= max_queries()
 
 
 def _workspace(t, nbytes, stream):

@@ -32,6 +32,9 @@ constexpr int kMaxQT = 16;    // query tiles per forward workgroup / narrow back
 constexpr int kWideQT = 32;   // query tiles of the wide backward
 constexpr int kMaxQ = kWideQT * 16;  // 512 queries
 constexpr int kChunk = 512;   // keys per workgroup (4 waves x 8 key tiles)
+// log of the softmax weight that the backward treats as zero: e^-40 = 2^-57.7, i.e. below the one bit the MFMA keeps under
+// fp32 (2^-25) beside the largest weight of a row of up to 2^16 keys (>= 2^-16), with 2^-16 to spare for the spread of dA - D
+constexpr float kNegligible = -40.f;
 
 __device__ __forceinline__ float bf2f(bf16_t v) { return __uint_as_float((unsigned)v << 16); }
 __device__ __forceinline__ bf16_t f2bf(float f) {
@@ -308,7 +311,11 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const bf16_t *__restrict_
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const bool ok = kbase + i < dm.Lk && q < dm.Lq;
-        float p = ok ? __expf(st[i] * dm.scale - lq1) : 0.f;
+        // the MFMA's adder floors every aligned term one bit below the fp32 result: beside the larger terms of a sum a weight
+        // below kNegligible can only lend its SIGN to that bit (-1e-26 takes 2^-24 of the largest term off dQ = x - x, which
+        // then is not 0).  Such weights count as zero in the backward.
+        const float arg = st[i] * dm.scale - lq1;
+        float p = (ok && arg > kNegligible) ? __expf(arg) : 0.f;
         float da = dat[i], a = p;
         if (DROP) {
           const bool kp = keep(seed, rb, kbase + i, dm.thresh24);
@@ -374,9 +381,15 @@ __global__ __launch_bounds__(256) void attn_mask_kernel(Dims dm, unsigned char *
   mask[t] = keep(eff_seed(dm), ((unsigned)bh * dm.Lq + q) * dm.Lk, key, dm.thresh24) ? 1 : 0;
 }
 
+// keep() hashes a 32-bit element index: with dropout, more than 2^32 attention weights would wrap it and repeat masks
+constexpr int kIndexRange = -2;
+#define BFHIP_ATTN_INDEX_MSG ": dropout hashes a 32-bit element index, B*H*Lq*Lk = %d*%d*%d*%d exceeds 2^32 (masks would repeat)"
+
 inline int make_dims(int B, int H, int Lq, int Lk, float scale, float dropout_p, unsigned long long seed,
                      const unsigned long long *seed_dev, Dims &dm) {
   if (B <= 0 || H <= 0 || Lq <= 0 || Lq > kMaxQ || Lk <= 0 || !(dropout_p >= 0.f && dropout_p < 1.f)) return -1;
+  const unsigned long long bh = (unsigned long long)B * H, lim = 1ull << 32;  // bh < 2^62, Lq <= 512: no 64-bit overflow below
+  if (dropout_p > 0.f && (bh > lim || bh * Lq > lim / (unsigned long long)Lk)) return kIndexRange;
   dm.B = B; dm.H = H; dm.Lq = Lq; dm.Lk = Lk; dm.E = H * kD;
   dm.nchunk = (Lk + kChunk - 1) / kChunk;
   dm.scale = scale;
@@ -407,7 +420,9 @@ BFHIP_EXPORT int bfhip_attn_fwd(const void *Q, const void *K, const void *V, int
                                 size_t workspace_bytes, void *stream_) {
   hipStream_t s = (hipStream_t)stream_;
   Dims dm;
-  BFHIP_REQUIRE(make_dims(B, H, Lq, Lk, scale, dropout_p, seed, seed_dev, dm) == 0, "attn_fwd: unsupported sizes B=%d H=%d Lq=%d Lk=%d (Lq <= 512, head dim 16)", B, H, Lq, Lk);
+  const int drc = make_dims(B, H, Lq, Lk, scale, dropout_p, seed, seed_dev, dm);
+  BFHIP_REQUIRE(drc != kIndexRange, "attn_fwd" BFHIP_ATTN_INDEX_MSG, B, H, Lq, Lk);
+  BFHIP_REQUIRE(drc == 0, "attn_fwd: unsupported sizes B=%d H=%d Lq=%d Lk=%d (Lq <= 512, head dim 16)", B, H, Lq, Lk);
   BFHIP_REQUIRE(Q && K && V && O && lse, "attn_fwd: null pointer");
   BFHIP_REQUIRE(((uintptr_t)Q % 8) == 0 && ((uintptr_t)K % 8) == 0 && ((uintptr_t)V % 8) == 0, "attn_fwd: tensors must be 8-byte aligned");
   BFHIP_REQUIRE_WORKSPACE(workspace, workspace_bytes, bfhip_attn_workspace_bytes(B, H, Lq, Lk), "attn_fwd");
@@ -430,7 +445,9 @@ BFHIP_EXPORT int bfhip_attn_bwd(const void *Q, const void *K, const void *V, con
                                 size_t workspace_bytes, void *stream_) {
   hipStream_t s = (hipStream_t)stream_;
   Dims dm;
-  BFHIP_REQUIRE(make_dims(B, H, Lq, Lk, scale, dropout_p, seed, seed_dev, dm) == 0, "attn_bwd: unsupported sizes");
+  const int drc = make_dims(B, H, Lq, Lk, scale, dropout_p, seed, seed_dev, dm);
+  BFHIP_REQUIRE(drc != kIndexRange, "attn_bwd" BFHIP_ATTN_INDEX_MSG, B, H, Lq, Lk);
+  BFHIP_REQUIRE(drc == 0, "attn_bwd: unsupported sizes");
   BFHIP_REQUIRE(Q && K && V && O && dO && lse && dQ && dK && dV, "attn_bwd: null pointer");
   BFHIP_REQUIRE_WORKSPACE(workspace, workspace_bytes, bfhip_attn_workspace_bytes(B, H, Lq, Lk), "attn_bwd");
   float *dqpart = (float *)((char *)workspace + align_up((size_t)B * H * dm.nchunk * Lq * sizeof(float2), 256));
@@ -452,7 +469,9 @@ BFHIP_EXPORT int bfhip_attn_dropout_mask(int B, int H, int Lq, int Lk, float dro
                                          const unsigned long long *seed_dev,
                                          unsigned char *mask, void *stream_) {
   Dims dm;
-  BFHIP_REQUIRE(make_dims(B, H, Lq, Lk, 1.f, dropout_p, seed, seed_dev, dm) == 0 && mask, "attn_dropout_mask: bad arguments");
+  const int drc = make_dims(B, H, Lq, Lk, 1.f, dropout_p, seed, seed_dev, dm);
+  BFHIP_REQUIRE(drc != kIndexRange, "attn_dropout_mask" BFHIP_ATTN_INDEX_MSG, B, H, Lq, Lk);
+  BFHIP_REQUIRE(drc == 0 && mask, "attn_dropout_mask: bad arguments");
   long long total = (long long)B * H * Lq * Lk;
   hipLaunchKernelGGL(attn_mask_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream_, dm, mask);
   return check_launch("attn_dropout_mask");

@@ -450,7 +450,7 @@ class _MHA(nn.Module):
 
         qp, kp, vp = proj(q, 0), proj(k, 1), proj(value, 2)
         p_drop = self.attn.dropout if self.training else 0.0
-        if split_attention.supported(qp, kp, vp, H) or split_attention.supported_wide(qp, kp, vp, H):
+        if split_attention.supported(qp, kp, vp, H, p_drop) or split_attention.supported_wide(qp, kp, vp, H, p_drop):
             # 200 (custom_data: 500) queries x 32 400 keys: split the key axis over the chip (csrc/attn.hip)
             o = split_attention.cross_attention(qp, kp, vp, H, p_drop)
         else:

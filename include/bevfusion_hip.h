@@ -387,7 +387,8 @@ int bfhip_xty(const void *X, const void *Y, long long K, int M, int N, int dtype
  *   key tile: dK / dV are still final per key, no extra workspace).  lse f32[B*H, Lq] (log-sum-exp of the scaled scores) links fwd and bwd.
  *   The key axis is split over the chip; combines run in a fixed order (bit-reproducible).  dropout_p in [0, 1): keep
  *   mask = counter hash of (seed, b, h, query, key), regenerated in the backward; bfhip_attn_dropout_mask writes it
- *   out (u8[B*H, Lq, Lk]) for tests.  The workspace is shared by fwd and bwd.
+ *   out (u8[B*H, Lq, Lk]) for tests.  The hashed element index is 32-bit: with dropout_p > 0 all three refuse
+ *   B*H*Lq*Lk > 2^32 (BFHIP_E_INVALID, before any launch).  The workspace is shared by fwd and bwd.
  * --------------------------------------------------------------------------------------- */
 int bfhip_attn_max_queries(void);
 size_t bfhip_attn_workspace_bytes(int B, int H, int Lq, int Lk);
