@@ -17,8 +17,12 @@
 //      perm(rank) of the sample, C stores by the owning thread (a scatter by nature).
 // No launch waits on another block of the same launch.  Sample descriptors travel in the kernel arguments.
 //
+// The three entries (bfhip_points_aug, _paste, _sweeps) share one host driver, run_points_aug: the checks of a whole batch, the
+// descriptor copy and the three launches per chunk are written once; an entry only says which of the two tables below it
+// brings, and those select among the four instantiations <HasPaste, HasSweeps> of kernels 1 and 3.
+//
 // ObjectSample's paste (bfhip_points_aug_paste) is a compile-time variant of kernels 1 and 3, HasPaste; the instantiation
-// without it is what bfhip_points_aug launches, as before.  With it a sample's row space is [m pasted rows ; n original rows]:
+// without it is what bfhip_points_aug launches.  With it a sample's row space is [m pasted rows ; n original rows]:
 // the pasted rows and the sample's K x 6 plane equations (K <= kMaxBoxes) live in device memory, their pointers and counts
 // travel beside the sample descriptors (Args + PasteArgs: 2.4 KB of the 4 KB of kernel arguments), stage_rows_paste fills
 // the tile from both sources when a block straddles the boundary and puts the plane table into LDS (6 KB at the cap) once
@@ -28,7 +32,7 @@
 // they see one sample of m + n rows.
 //
 // LoadPointsFromMultiSweeps (bfhip_points_aug_sweeps) is a second compile-time variant, HasSweeps, alone or with HasPaste; the
-// instantiations without it are what the two entries above launch, as before.  A sample's own rows are then [keyframe ; sweep
+// instantiations without it are what the two entries above launch.  A sample's own rows are then [keyframe ; sweep
 // 1 ; ... ; sweep S], still ONE contiguous buffer (stage_rows / stage_rows_paste do not change), cut into at most kMaxSegments
 // segments {first row, flags, dt, radius, double m[9], double t[3]} (112 B).  The tables live in device memory -- 16 x 16 of
 // them would not fit the kernel arguments -- and only a pointer and a count per sample travel beside Args / PasteArgs; a block
@@ -43,6 +47,7 @@
 // walk follows the cycle of r, which comes back to r < n: it terminates, and the restriction is a bijection of [0, n)).  Round
 // i: (L, R) <- (R, L ^ (mix(R + key_i) & (2^h - 1))), mix the 32-bit finaliser below; at the end value = L << h | R.
 #include "common.h"
+#include "points_tile.h"
 
 namespace bfhip {
 namespace {
@@ -128,13 +133,6 @@ __device__ __forceinline__ int sample_of_block(const Args &a, int b) {
   return s;
 }
 
-// the block's rows into LDS: rows [first, first + rows) of src, C floats each, consecutive lanes consecutive dwords
-__device__ __forceinline__ void stage_rows(const float *__restrict__ src, long long first, int rows, int C, float *tile) {
-  const float *p = src + first * C;
-  const int nd = rows * C;
-  for (int d = threadIdx.x; d < nd; d += kBlock) tile[d] = p[d];
-}
-
 // transformed xyz of one row and whether it is kept
 __device__ __forceinline__ bool transform(const Sample &sp, float &x, float &y, float &z) {
   const int f = sp.flags;
@@ -168,7 +166,7 @@ __device__ __forceinline__ void stage_rows_paste(const Paste &pd, const float *_
   const int bd = b < 0 ? 0 : (b > nd ? nd : (int)b);
   const long long p0 = first * C, s0 = (first - pd.m) * C;  // s0 + d >= 0 wherever d >= bd
   for (int d = threadIdx.x; d < nd; d += kBlock) tile[d] = d < bd ? pd.pts[p0 + d] : src[s0 + d];
-  const int np = pd.K * 24;
+  const int np = pd.K * kPlaneFloats;
   for (int d = threadIdx.x; d < np; d += kBlock) planes[d] = pd.planes[d];
 }
 
@@ -176,12 +174,10 @@ __device__ __forceinline__ void stage_rows_paste(const Paste &pd, const float *_
 // the same plane at the same time (a broadcast), and a box is left at its first plane with sign >= 0
 __device__ __forceinline__ bool inside_any_box(const float *planes, int K, float x, float y, float z) {
   for (int j = 0; j < K; ++j) {
-    const float *pl = planes + j * 24;
+    const float *pl = planes + j * kPlaneFloats;
     bool inside = true;
     for (int k = 0; k < 6; ++k) {
-      const float sign = __fadd_rn(
-          __fadd_rn(__fadd_rn(__fmul_rn(x, pl[4 * k]), __fmul_rn(y, pl[4 * k + 1])), __fmul_rn(z, pl[4 * k + 2])), pl[4 * k + 3]);
-      if (!(sign < 0.f)) {
+      if (!(plane_sign(pl + 4 * k, x, y, z) < 0.f)) {  // NaN: left
         inside = false;
         break;
       }
@@ -238,7 +234,7 @@ __device__ __forceinline__ void count_block(const Args &a, const PasteArgs *pa, 
                                             int *__restrict__ block_counts) {
   __shared__ float tile[kBlock * kMaxC];
   __shared__ int wsum[kWaves];
-  __shared__ float planes[HasPaste ? kMaxBoxes * 24 : 1];  // without a paste: unused, and gone from the kernel
+  __shared__ float planes[HasPaste ? kMaxBoxes * kPlaneFloats : 1];  // without a paste: unused, and gone from the kernel
   __shared__ uint32_t segs[HasSweeps ? kMaxSegments * kSegmentDwords : 1];
   const int si = sample_of_block(a, blockIdx.x);
   const Sample &sp = a.s[si];
@@ -247,7 +243,7 @@ __device__ __forceinline__ void count_block(const Args &a, const PasteArgs *pa, 
   if constexpr (HasPaste) {
     stage_rows_paste(pa->p[si], sp.src, first, rows, a.C, tile, planes);
   } else {
-    stage_rows(sp.src, first, rows, a.C, tile);
+    stage_rows<kBlock>(sp.src, first, rows, a.C, tile);
   }
   if constexpr (HasSweeps) stage_segments(wa->w[si], segs);
   __syncthreads();
@@ -334,7 +330,7 @@ __device__ __forceinline__ void write_block(const Args &a, const PasteArgs *pa, 
   __shared__ float tile[kBlock * kMaxC];
   __shared__ float packed[kBlock * kMaxC];
   __shared__ int wsum[kWaves];
-  __shared__ float planes[HasPaste ? kMaxBoxes * 24 : 1];
+  __shared__ float planes[HasPaste ? kMaxBoxes * kPlaneFloats : 1];
   __shared__ uint32_t segs[HasSweeps ? kMaxSegments * kSegmentDwords : 1];
   const int si = sample_of_block(a, blockIdx.x);
   const Sample &sp = a.s[si];
@@ -344,7 +340,7 @@ __device__ __forceinline__ void write_block(const Args &a, const PasteArgs *pa, 
   if constexpr (HasPaste) {
     stage_rows_paste(pa->p[si], sp.src, first, rows, C, tile, planes);
   } else {
-    stage_rows(sp.src, first, rows, C, tile);
+    stage_rows<kBlock>(sp.src, first, rows, C, tile);
   }
   if constexpr (HasSweeps) stage_segments(wa->w[si], segs);
   __syncthreads();
@@ -421,219 +417,99 @@ __global__ __launch_bounds__(kBlock) void points_write_paste_sweeps_kernel(Args 
 
 long long blocks_of(long long n) { return (n + kBlock - 1) / kBlock; }
 
-}  // namespace
-}  // namespace bfhip
-
-using namespace bfhip;
-
-BFHIP_EXPORT int bfhip_points_aug_block(void) { return kBlock; }
-
-BFHIP_EXPORT size_t bfhip_points_aug_workspace_bytes(long long total_rows, int n_samples) {
-  if (total_rows < 0 || n_samples < 0) return 0;
-  // one int per block; a sample's last block may be partial
-  return align_up((size_t)(blocks_of(total_rows) + n_samples) * sizeof(int), 256);
+// the descriptor copy: a sample of `rows` rows (pasted ones included) from block `block0` of the launch and output row `row0`
+void fill(Sample &d, const bfhip_points_aug_sample &s, int rows, int block0, int row0) {
+  d.src = s.points;
+  d.n = rows;
+  d.block0 = block0;
+  d.row0 = row0;
+  d.flags = s.flags;
+  for (int k = 0; k < 9; ++k) d.r[k] = s.rot[k];
+  for (int k = 0; k < 3; ++k) d.t[k] = s.trans[k];
+  d.s = s.scale;
+  for (int k = 0; k < 6; ++k) d.range[k] = s.range[k];
+  for (int k = 0; k < kRounds; ++k) d.key[k] = s.keys[k];
 }
 
-BFHIP_EXPORT int bfhip_points_aug(const bfhip_points_aug_sample *samples_host, int n_samples, int C, float *out, int32_t *kept,
-                                  void *workspace, size_t workspace_bytes, void *stream) {
-  BFHIP_REQUIRE(samples_host && kept, "points_aug: a required pointer is NULL");
-  BFHIP_REQUIRE(n_samples >= 1, "points_aug: n_samples=%d", n_samples);
-  BFHIP_REQUIRE(C >= 3 && C <= kMaxC, "points_aug: %d columns (3 .. %d)", C, kMaxC);
+// the count and the write launch of a chunk: each kernel receives the argument structs of its variant and no others
+void launch_count(bool paste, bool sweeps, unsigned blocks, hipStream_t st, const Args &a, const PasteArgs &pa,
+                  const SweepArgs &wa, int *counts) {
+  if (paste && sweeps)
+    hipLaunchKernelGGL(points_count_paste_sweeps_kernel, dim3(blocks), dim3(kBlock), 0, st, a, pa, wa, counts);
+  else if (paste)
+    hipLaunchKernelGGL(points_count_paste_kernel, dim3(blocks), dim3(kBlock), 0, st, a, pa, counts);
+  else if (sweeps)
+    hipLaunchKernelGGL(points_count_sweeps_kernel, dim3(blocks), dim3(kBlock), 0, st, a, wa, counts);
+  else
+    hipLaunchKernelGGL(points_count_kernel, dim3(blocks), dim3(kBlock), 0, st, a, counts);
+}
+
+void launch_write(bool paste, bool sweeps, unsigned blocks, hipStream_t st, const Args &a, const PasteArgs &pa,
+                  const SweepArgs &wa, const int *offs, const int *kept, float *out) {
+  if (paste && sweeps)
+    hipLaunchKernelGGL(points_write_paste_sweeps_kernel, dim3(blocks), dim3(kBlock), 0, st, a, pa, wa, offs, kept, out);
+  else if (paste)
+    hipLaunchKernelGGL(points_write_paste_kernel, dim3(blocks), dim3(kBlock), 0, st, a, pa, offs, kept, out);
+  else if (sweeps)
+    hipLaunchKernelGGL(points_write_sweeps_kernel, dim3(blocks), dim3(kBlock), 0, st, a, wa, offs, kept, out);
+  else
+    hipLaunchKernelGGL(points_write_kernel, dim3(blocks), dim3(kBlock), 0, st, a, offs, kept, out);
+}
+
+// The host side of the three entries, `what` the entry's name in its messages.  pastes / sweeps: one descriptor per sample, or
+// NULL for the kernels without that variant (a given table selects its variant even when every descriptor in it is empty).
+// Everything is checked before the first launch: a rejected call launches nothing.
+int run_points_aug(const char *what, const bfhip_points_aug_sample *samples, const bfhip_points_aug_paste_desc *pastes,
+                   const bfhip_points_aug_sweeps_desc *sweeps, int min_C, int n_samples, int C, float *out, int32_t *kept,
+                   void *workspace, size_t workspace_bytes, void *stream) {
+  BFHIP_REQUIRE(samples && kept, "%s: a required pointer is NULL", what);
+  BFHIP_REQUIRE(n_samples >= 1, "%s: n_samples=%d", what, n_samples);
+  BFHIP_REQUIRE(C >= min_C && C <= kMaxC, "%s: %d columns (%d .. %d%s)", what, C, min_C, kMaxC,
+                sweeps ? ": column 4 takes the time lag" : "");
   long long total = 0;
   for (int i = 0; i < n_samples; ++i) {
-    const bfhip_points_aug_sample &s = samples_host[i];
-    BFHIP_REQUIRE(s.n >= 0 && (s.n == 0 || s.points), "points_aug: sample %d: n=%d points=%p", i, s.n, (const void *)s.points);
-    BFHIP_REQUIRE((s.flags & ~63) == 0, "points_aug: sample %d: flags 0x%x", i, s.flags);
-    BFHIP_REQUIRE(((uintptr_t)s.points & 3) == 0, "points_aug: sample %d: points not 4-byte aligned", i);
+    const bfhip_points_aug_sample &s = samples[i];
+    BFHIP_REQUIRE(s.n >= 0 && (s.n == 0 || s.points), "%s: sample %d: n=%d points=%p", what, i, s.n, (const void *)s.points);
+    BFHIP_REQUIRE((s.flags & ~63) == 0, "%s: sample %d: flags 0x%x", what, i, s.flags);
+    BFHIP_REQUIRE(((uintptr_t)s.points & 3) == 0, "%s: sample %d: points not 4-byte aligned", what, i);
     total += s.n;
-  }
-  BFHIP_REQUIRE(total <= 0x7fffffffll, "points_aug: %lld rows in all (below 2^31)", total);
-  BFHIP_REQUIRE(total == 0 || out, "points_aug: out is NULL");
-  BFHIP_REQUIRE(workspace_bytes >= bfhip_points_aug_workspace_bytes(total, n_samples) && (workspace || total == 0),
-                "points_aug: workspace of %zu bytes, %zu needed", workspace_bytes,
-                bfhip_points_aug_workspace_bytes(total, n_samples));
-  int *counts = (int *)workspace;
-  long long row0 = 0;
-  for (int first = 0; first < n_samples; first += kMaxSamples) {
-    const int n = n_samples - first < kMaxSamples ? n_samples - first : kMaxSamples;
-    Args a;
-    a.n_samples = n;
-    a.C = C;
-    long long blocks = 0;
-    for (int i = 0; i < kMaxSamples; ++i) {
-      Sample &d = a.s[i];
-      if (i >= n) {
-        d = a.s[n - 1];
-        d.n = 0;
-        d.block0 = (int)blocks;
-        continue;
+    if (sweeps) {
+      const bfhip_points_aug_sweeps_desc &w = sweeps[i];
+      BFHIP_REQUIRE(w.n_segments >= 0 && w.n_segments <= kMaxSegments && (w.n_segments == 0 || w.segments),
+                    "%s: sample %d: n_segments=%d (0 .. %d) segments=%p", what, i, w.n_segments, kMaxSegments,
+                    (const void *)w.segments);
+      BFHIP_REQUIRE(((uintptr_t)w.segments & 7) == 0, "%s: sample %d: segments not 8-byte aligned", what, i);
+      if (w.n_segments > 0) {
+        BFHIP_REQUIRE(w.first[0] == 0 && w.first[w.n_segments] == s.n,
+                      "%s: sample %d: boundaries run from %d to %d, the sample's rows from 0 to %d", what, i, w.first[0],
+                      w.first[w.n_segments], s.n);
+        for (int k = 0; k < w.n_segments; ++k)
+          BFHIP_REQUIRE(w.first[k] <= w.first[k + 1], "%s: sample %d: boundary %d (%d) is below boundary %d (%d)", what, i, k + 1,
+                        w.first[k + 1], k, w.first[k]);
       }
-      const bfhip_points_aug_sample &s = samples_host[first + i];
-      d.src = s.points;
-      d.n = s.n;
-      d.block0 = (int)blocks;
-      d.row0 = (int)row0;
-      d.flags = s.flags;
-      for (int k = 0; k < 9; ++k) d.r[k] = s.rot[k];
-      for (int k = 0; k < 3; ++k) d.t[k] = s.trans[k];
-      d.s = s.scale;
-      for (int k = 0; k < 6; ++k) d.range[k] = s.range[k];
-      for (int k = 0; k < kRounds; ++k) d.key[k] = s.keys[k];
-      blocks += blocks_of(s.n);
-      row0 += s.n;
     }
-    if (blocks > 0) {
-      hipLaunchKernelGGL(points_count_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, a, counts);
-      const int rc = check_launch("points_aug count");
-      if (rc != BFHIP_OK) return rc;
-    }
-    // always launched: an all-empty chunk still needs its kept counts (zero) written
-    hipLaunchKernelGGL(points_scan_kernel, dim3(1), dim3(kScanBlock), 0, (hipStream_t)stream, a, (int)blocks, counts,
-                       kept + first);
-    int rc = check_launch("points_aug scan");
-    if (rc != BFHIP_OK) return rc;
-    if (blocks > 0) {
-      hipLaunchKernelGGL(points_write_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, a, counts,
-                         kept + first, out);
-      rc = check_launch("points_aug write");
-      if (rc != BFHIP_OK) return rc;
-    }
-    counts += blocks;
-  }
-  return BFHIP_OK;
-}
-
-BFHIP_EXPORT int bfhip_points_aug_max_boxes(void) { return kMaxBoxes; }
-
-BFHIP_EXPORT int bfhip_points_aug_paste(const bfhip_points_aug_sample *samples_host,
-                                        const bfhip_points_aug_paste_desc *pastes_host, int n_samples, int C, float *out,
-                                        int32_t *kept, void *workspace, size_t workspace_bytes, void *stream) {
-  BFHIP_REQUIRE(samples_host && pastes_host && kept, "points_aug_paste: a required pointer is NULL");
-  BFHIP_REQUIRE(n_samples >= 1, "points_aug_paste: n_samples=%d", n_samples);
-  BFHIP_REQUIRE(C >= 3 && C <= kMaxC, "points_aug_paste: %d columns (3 .. %d)", C, kMaxC);
-  long long total = 0;
-  for (int i = 0; i < n_samples; ++i) {
-    const bfhip_points_aug_sample &s = samples_host[i];
-    const bfhip_points_aug_paste_desc &p = pastes_host[i];
-    BFHIP_REQUIRE(s.n >= 0 && (s.n == 0 || s.points), "points_aug_paste: sample %d: n=%d points=%p", i, s.n,
-                  (const void *)s.points);
-    BFHIP_REQUIRE((s.flags & ~63) == 0, "points_aug_paste: sample %d: flags 0x%x", i, s.flags);
-    BFHIP_REQUIRE(p.n_points >= 0 && (p.n_points == 0 || p.points), "points_aug_paste: sample %d: n_points=%d points=%p", i,
-                  p.n_points, (const void *)p.points);
-    BFHIP_REQUIRE(p.n_boxes >= 0 && p.n_boxes <= kMaxBoxes && (p.n_boxes == 0 || p.planes),
-                  "points_aug_paste: sample %d: n_boxes=%d (0 .. %d) planes=%p", i, p.n_boxes, kMaxBoxes, (const void *)p.planes);
-    BFHIP_REQUIRE((((uintptr_t)s.points | (uintptr_t)p.points | (uintptr_t)p.planes) & 3) == 0,
-                  "points_aug_paste: sample %d: a pointer is not 4-byte aligned", i);
-    total += (long long)s.n + p.n_points;
-  }
-  BFHIP_REQUIRE(total <= 0x7fffffffll, "points_aug_paste: %lld rows in all (below 2^31)", total);
-  BFHIP_REQUIRE(total == 0 || out, "points_aug_paste: out is NULL");
-  BFHIP_REQUIRE(workspace_bytes >= bfhip_points_aug_workspace_bytes(total, n_samples) && (workspace || total == 0),
-                "points_aug_paste: workspace of %zu bytes, %zu needed", workspace_bytes,
-                bfhip_points_aug_workspace_bytes(total, n_samples));
-  int *counts = (int *)workspace;
-  long long row0 = 0;
-  for (int first = 0; first < n_samples; first += kMaxSamples) {
-    const int n = n_samples - first < kMaxSamples ? n_samples - first : kMaxSamples;
-    Args a;
-    PasteArgs pa;
-    a.n_samples = n;
-    a.C = C;
-    long long blocks = 0;
-    for (int i = 0; i < kMaxSamples; ++i) {
-      Sample &d = a.s[i];
-      Paste &q = pa.p[i];
-      if (i >= n) {  // never reached by a block: block0 = the launch's block count
-        d = a.s[n - 1];
-        d.n = 0;
-        d.block0 = (int)blocks;
-        q = Paste{nullptr, nullptr, 0, 0};
-        continue;
-      }
-      const bfhip_points_aug_sample &s = samples_host[first + i];
-      const bfhip_points_aug_paste_desc &p = pastes_host[first + i];
-      const long long rows = (long long)s.n + p.n_points;
-      d.src = s.points;
-      d.n = (int)rows;  // the row space: pasted rows, then the original ones
-      d.block0 = (int)blocks;
-      d.row0 = (int)row0;
-      d.flags = s.flags;
-      for (int k = 0; k < 9; ++k) d.r[k] = s.rot[k];
-      for (int k = 0; k < 3; ++k) d.t[k] = s.trans[k];
-      d.s = s.scale;
-      for (int k = 0; k < 6; ++k) d.range[k] = s.range[k];
-      for (int k = 0; k < kRounds; ++k) d.key[k] = s.keys[k];
-      q = Paste{p.points, p.planes, p.n_points, p.n_boxes};
-      blocks += blocks_of(rows);
-      row0 += rows;
-    }
-    if (blocks > 0) {
-      hipLaunchKernelGGL(points_count_paste_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, a, pa, counts);
-      const int rc = check_launch("points_aug_paste count");
-      if (rc != BFHIP_OK) return rc;
-    }
-    hipLaunchKernelGGL(points_scan_kernel, dim3(1), dim3(kScanBlock), 0, (hipStream_t)stream, a, (int)blocks, counts,
-                       kept + first);
-    int rc = check_launch("points_aug_paste scan");
-    if (rc != BFHIP_OK) return rc;
-    if (blocks > 0) {
-      hipLaunchKernelGGL(points_write_paste_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, a, pa, counts,
-                         kept + first, out);
-      rc = check_launch("points_aug_paste write");
-      if (rc != BFHIP_OK) return rc;
-    }
-    counts += blocks;
-  }
-  return BFHIP_OK;
-}
-
-BFHIP_EXPORT int bfhip_points_aug_max_sweeps(void) { return kMaxSegments; }
-
-BFHIP_EXPORT int bfhip_points_aug_sweeps(const bfhip_points_aug_sample *samples_host,
-                                         const bfhip_points_aug_paste_desc *pastes_host,
-                                         const bfhip_points_aug_sweeps_desc *sweeps_host, int n_samples, int C, float *out,
-                                         int32_t *kept, void *workspace, size_t workspace_bytes, void *stream) {
-  BFHIP_REQUIRE(samples_host && sweeps_host && kept, "points_aug_sweeps: a required pointer is NULL");
-  BFHIP_REQUIRE(n_samples >= 1, "points_aug_sweeps: n_samples=%d", n_samples);
-  BFHIP_REQUIRE(C >= 5 && C <= kMaxC, "points_aug_sweeps: %d columns (5 .. %d: column 4 takes the time lag)", C, kMaxC);
-  long long total = 0;
-  for (int i = 0; i < n_samples; ++i) {
-    const bfhip_points_aug_sample &s = samples_host[i];
-    const bfhip_points_aug_sweeps_desc &w = sweeps_host[i];
-    BFHIP_REQUIRE(s.n >= 0 && (s.n == 0 || s.points), "points_aug_sweeps: sample %d: n=%d points=%p", i, s.n,
-                  (const void *)s.points);
-    BFHIP_REQUIRE((s.flags & ~63) == 0, "points_aug_sweeps: sample %d: flags 0x%x", i, s.flags);
-    BFHIP_REQUIRE(((uintptr_t)s.points & 3) == 0, "points_aug_sweeps: sample %d: points not 4-byte aligned", i);
-    BFHIP_REQUIRE(w.n_segments >= 0 && w.n_segments <= kMaxSegments && (w.n_segments == 0 || w.segments),
-                  "points_aug_sweeps: sample %d: n_segments=%d (0 .. %d) segments=%p", i, w.n_segments, kMaxSegments,
-                  (const void *)w.segments);
-    BFHIP_REQUIRE(((uintptr_t)w.segments & 7) == 0, "points_aug_sweeps: sample %d: segments not 8-byte aligned", i);
-    if (w.n_segments > 0) {
-      BFHIP_REQUIRE(w.first[0] == 0 && w.first[w.n_segments] == s.n,
-                    "points_aug_sweeps: sample %d: boundaries run from %d to %d, the sample's rows from 0 to %d", i, w.first[0],
-                    w.first[w.n_segments], s.n);
-      for (int k = 0; k < w.n_segments; ++k)
-        BFHIP_REQUIRE(w.first[k] <= w.first[k + 1], "points_aug_sweeps: sample %d: boundary %d (%d) is below boundary %d (%d)", i,
-                      k + 1, w.first[k + 1], k, w.first[k]);
-    }
-    total += s.n;
-    if (pastes_host) {
-      const bfhip_points_aug_paste_desc &p = pastes_host[i];
-      BFHIP_REQUIRE(p.n_points >= 0 && (p.n_points == 0 || p.points), "points_aug_sweeps: sample %d: n_points=%d points=%p", i,
-                    p.n_points, (const void *)p.points);
+    if (pastes) {
+      const bfhip_points_aug_paste_desc &p = pastes[i];
+      BFHIP_REQUIRE(p.n_points >= 0 && (p.n_points == 0 || p.points), "%s: sample %d: n_points=%d points=%p", what, i, p.n_points,
+                    (const void *)p.points);
       BFHIP_REQUIRE(p.n_boxes >= 0 && p.n_boxes <= kMaxBoxes && (p.n_boxes == 0 || p.planes),
-                    "points_aug_sweeps: sample %d: n_boxes=%d (0 .. %d) planes=%p", i, p.n_boxes, kMaxBoxes,
-                    (const void *)p.planes);
-      BFHIP_REQUIRE((((uintptr_t)p.points | (uintptr_t)p.planes) & 3) == 0,
-                    "points_aug_sweeps: sample %d: a paste pointer is not 4-byte aligned", i);
+                    "%s: sample %d: n_boxes=%d (0 .. %d) planes=%p", what, i, p.n_boxes, kMaxBoxes, (const void *)p.planes);
+      BFHIP_REQUIRE((((uintptr_t)p.points | (uintptr_t)p.planes) & 3) == 0, "%s: sample %d: a paste pointer is not 4-byte aligned",
+                    what, i);
       total += p.n_points;
     }
   }
-  BFHIP_REQUIRE(total <= 0x7fffffffll, "points_aug_sweeps: %lld rows in all (below 2^31)", total);
-  BFHIP_REQUIRE(total == 0 || out, "points_aug_sweeps: out is NULL");
-  BFHIP_REQUIRE(workspace_bytes >= bfhip_points_aug_workspace_bytes(total, n_samples) && (workspace || total == 0),
-                "points_aug_sweeps: workspace of %zu bytes, %zu needed", workspace_bytes,
-                bfhip_points_aug_workspace_bytes(total, n_samples));
+  BFHIP_REQUIRE(total <= 0x7fffffffll, "%s: %lld rows in all (below 2^31)", what, total);
+  BFHIP_REQUIRE(total == 0 || out, "%s: out is NULL", what);
+  const size_t need = bfhip_points_aug_workspace_bytes(total, n_samples);
+  BFHIP_REQUIRE(workspace_bytes >= need && (workspace || total == 0), "%s: workspace of %zu bytes, %zu needed", what,
+                workspace_bytes, need);
+  const hipStream_t st = (hipStream_t)stream;
+  auto launched = [what](const char *kernel) {
+    char label[64];
+    snprintf(label, sizeof(label), "%s %s", what, kernel);
+    return check_launch(label);
+  };
   int *counts = (int *)workspace;
   long long row0 = 0;
   for (int first = 0; first < n_samples; first += kMaxSamples) {
@@ -645,62 +521,73 @@ BFHIP_EXPORT int bfhip_points_aug_sweeps(const bfhip_points_aug_sample *samples_
     a.C = C;
     long long blocks = 0;
     for (int i = 0; i < kMaxSamples; ++i) {
-      Sample &d = a.s[i];
-      Paste &q = pa.p[i];
-      Sweeps &g = wa.w[i];
-      if (i >= n) {  // never reached by a block: block0 = the launch's block count
-        d = a.s[n - 1];
-        d.n = 0;
-        d.block0 = (int)blocks;
-        q = Paste{nullptr, nullptr, 0, 0};
-        g = Sweeps{nullptr, 0};
-        continue;
-      }
-      const bfhip_points_aug_sample &s = samples_host[first + i];
-      q = Paste{nullptr, nullptr, 0, 0};
-      if (pastes_host) {
-        const bfhip_points_aug_paste_desc &p = pastes_host[first + i];
-        q = Paste{p.points, p.planes, p.n_points, p.n_boxes};
-      }
-      g = Sweeps{sweeps_host[first + i].segments, sweeps_host[first + i].n_segments};
-      const long long rows = (long long)s.n + q.m;
-      d.src = s.points;
-      d.n = (int)rows;  // the row space: pasted rows, then the keyframe and the sweeps
-      d.block0 = (int)blocks;
-      d.row0 = (int)row0;
-      d.flags = s.flags;
-      for (int k = 0; k < 9; ++k) d.r[k] = s.rot[k];
-      for (int k = 0; k < 3; ++k) d.t[k] = s.trans[k];
-      d.s = s.scale;
-      for (int k = 0; k < 6; ++k) d.range[k] = s.range[k];
-      for (int k = 0; k < kRounds; ++k) d.key[k] = s.keys[k];
+      // a slot i >= n is never reached by a block: the last real descriptor with no rows, block0 = the launch's block count
+      const bool real = i < n;
+      const int j = first + (real ? i : n - 1);
+      pa.p[i] = real && pastes ? Paste{pastes[j].points, pastes[j].planes, pastes[j].n_points, pastes[j].n_boxes}
+                               : Paste{nullptr, nullptr, 0, 0};
+      wa.w[i] = real && sweeps ? Sweeps{sweeps[j].segments, sweeps[j].n_segments} : Sweeps{nullptr, 0};
+      // the row space: pasted rows, then the sample's own (the keyframe and the sweeps)
+      const long long rows = real ? (long long)samples[j].n + pa.p[i].m : 0;
+      fill(a.s[i], samples[j], (int)rows, (int)blocks, (int)row0);
       blocks += blocks_of(rows);
       row0 += rows;
     }
+    int rc;
     if (blocks > 0) {
-      if (pastes_host)
-        hipLaunchKernelGGL(points_count_paste_sweeps_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, a, pa,
-                           wa, counts);
-      else
-        hipLaunchKernelGGL(points_count_sweeps_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, a, wa, counts);
-      const int rc = check_launch("points_aug_sweeps count");
-      if (rc != BFHIP_OK) return rc;
+      launch_count(pastes != nullptr, sweeps != nullptr, (unsigned)blocks, st, a, pa, wa, counts);
+      if ((rc = launched("count")) != BFHIP_OK) return rc;
     }
-    hipLaunchKernelGGL(points_scan_kernel, dim3(1), dim3(kScanBlock), 0, (hipStream_t)stream, a, (int)blocks, counts,
-                       kept + first);
-    int rc = check_launch("points_aug_sweeps scan");
-    if (rc != BFHIP_OK) return rc;
+    // always launched: an all-empty chunk still needs its kept counts (zero) written
+    hipLaunchKernelGGL(points_scan_kernel, dim3(1), dim3(kScanBlock), 0, st, a, (int)blocks, counts, kept + first);
+    if ((rc = launched("scan")) != BFHIP_OK) return rc;
     if (blocks > 0) {
-      if (pastes_host)
-        hipLaunchKernelGGL(points_write_paste_sweeps_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, a, pa,
-                           wa, counts, kept + first, out);
-      else
-        hipLaunchKernelGGL(points_write_sweeps_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, a, wa, counts,
-                           kept + first, out);
-      rc = check_launch("points_aug_sweeps write");
-      if (rc != BFHIP_OK) return rc;
+      launch_write(pastes != nullptr, sweeps != nullptr, (unsigned)blocks, st, a, pa, wa, counts, kept + first, out);
+      if ((rc = launched("write")) != BFHIP_OK) return rc;
     }
     counts += blocks;
   }
   return BFHIP_OK;
 }
+
+}  // namespace
+}  // namespace bfhip
+
+using namespace bfhip;
+
+BFHIP_EXPORT int bfhip_points_aug_block(void) { return kBlock; }
+
+BFHIP_EXPORT int bfhip_points_aug_max_boxes(void) { return kMaxBoxes; }
+
+BFHIP_EXPORT int bfhip_points_aug_max_sweeps(void) { return kMaxSegments; }
+
+BFHIP_EXPORT size_t bfhip_points_aug_workspace_bytes(long long total_rows, int n_samples) {
+  if (total_rows < 0 || n_samples < 0) return 0;
+  // one int per block; a sample's last block may be partial
+  return align_up((size_t)(blocks_of(total_rows) + n_samples) * sizeof(int), 256);
+}
+
+BFHIP_EXPORT int bfhip_points_aug(const bfhip_points_aug_sample *samples_host, int n_samples, int C, float *out, int32_t *kept,
+                                  void *workspace, size_t workspace_bytes, void *stream) {
+  return run_points_aug("points_aug", samples_host, nullptr, nullptr, 3, n_samples, C, out, kept, workspace, workspace_bytes,
+                        stream);
+}
+
+BFHIP_EXPORT int bfhip_points_aug_paste(const bfhip_points_aug_sample *samples_host,
+                                        const bfhip_points_aug_paste_desc *pastes_host, int n_samples, int C, float *out,
+                                        int32_t *kept, void *workspace, size_t workspace_bytes, void *stream) {
+  BFHIP_REQUIRE(pastes_host, "points_aug_paste: a required pointer is NULL");
+  return run_points_aug("points_aug_paste", samples_host, pastes_host, nullptr, 3, n_samples, C, out, kept, workspace,
+                        workspace_bytes, stream);
+}
+
+// pastes_host may be NULL: the kernels without the paste
+BFHIP_EXPORT int bfhip_points_aug_sweeps(const bfhip_points_aug_sample *samples_host,
+                                         const bfhip_points_aug_paste_desc *pastes_host,
+                                         const bfhip_points_aug_sweeps_desc *sweeps_host, int n_samples, int C, float *out,
+                                         int32_t *kept, void *workspace, size_t workspace_bytes, void *stream) {
+  BFHIP_REQUIRE(sweeps_host, "points_aug_sweeps: a required pointer is NULL");
+  return run_points_aug("points_aug_sweeps", samples_host, pastes_host, sweeps_host, 5, n_samples, C, out, kept, workspace,
+                        workspace_bytes, stream);
+}
+

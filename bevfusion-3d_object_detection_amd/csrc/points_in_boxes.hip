@@ -8,7 +8,7 @@
 //
 // Three launches, count -> scan -> ranked write (points_aug.hip, voxelize.hip 2a-2c):
 //   1. pib_count_kernel: one workgroup of kBlock threads per kBlock consecutive rows, staged through LDS with coalesced dword
-//      reads (stage_rows of points_aug.hip).  The plane table goes through LDS in chunks of kChunk = 64 boxes (24 floats per
+//      reads (stage_rows of points_tile.h).  The plane table goes through LDS in chunks of kChunk = 64 boxes (24 floats per
 //      box, 6 KB); all lanes of a wave read the same plane at the same time (an LDS broadcast) and leave a box at its first plane
 //      with sign >= 0.  Per box one wave __ballot: its popcount is the wave's member count, its bit of the lane goes into the
 //      lane's 64-bit membership word of the chunk.  Out: the words, member[n][W], W = ceil(K / 64), and the per (box, workgroup)
@@ -24,6 +24,7 @@
 // No atomics anywhere: every output is a pure function of the inputs, the same bytes on every run.  No launch waits on another
 // block of the same launch.
 #include "common.h"
+#include "points_tile.h"
 
 namespace bfhip {
 namespace {
@@ -33,15 +34,7 @@ constexpr int kWaves = kBlock / kWave;
 constexpr int kMaxC = 8;
 constexpr int kChunk = 64;         // boxes per LDS plane table and per membership word
 constexpr int kMaxBoxes = 256;     // boxes per call: the gather scans counts[K] with one thread per box
-constexpr int kPlaneFloats = 24;   // 6 planes x (n0, n1, n2, d)
 static_assert(kChunk == kWave && kMaxBoxes <= kBlock, "one lane per box of a chunk, one thread per box of a call");
-
-// rows [first, first + rows) of src, C floats each, into LDS: consecutive lanes load consecutive dwords
-__device__ __forceinline__ void stage_rows(const float *__restrict__ src, long long first, int rows, int C, float *tile) {
-  const float *p = src + first * C;
-  const int nd = rows * C;
-  for (int d = threadIdx.x; d < nd; d += kBlock) tile[d] = p[d];
-}
 
 __global__ __launch_bounds__(kBlock) void pib_count_kernel(const float *__restrict__ points, int n, int C,
                                                            const float *__restrict__ planes_g, int K, int blocks,
@@ -54,7 +47,7 @@ __global__ __launch_bounds__(kBlock) void pib_count_kernel(const float *__restri
   const long long first = (long long)blockIdx.x * kBlock;
   const int rows = n - first < kBlock ? (int)(n - first) : kBlock;
   const int W = (K + kChunk - 1) / kChunk;
-  stage_rows(points, first, rows, C, tile);
+  stage_rows<kBlock>(points, first, rows, C, tile);
   __syncthreads();
   float x = 0.f, y = 0.f, z = 0.f;
   const bool live = t < rows;
@@ -70,9 +63,7 @@ __global__ __launch_bounds__(kBlock) void pib_count_kernel(const float *__restri
       bool inside = live;
       if (inside) {
         for (int k = 0; k < 6; ++k) {
-          const float sign = __fadd_rn(
-              __fadd_rn(__fadd_rn(__fmul_rn(x, pl[4 * k]), __fmul_rn(y, pl[4 * k + 1])), __fmul_rn(z, pl[4 * k + 2])), pl[4 * k + 3]);
-          if (sign >= 0.f) {  // NaN: not left
+          if (plane_sign(pl + 4 * k, x, y, z) >= 0.f) {  // NaN: not left
             inside = false;
             break;
           }
@@ -148,7 +139,7 @@ __global__ __launch_bounds__(kBlock) void pib_gather_kernel(const float *__restr
   const long long first = (long long)blockIdx.x * kBlock;
   const int rows = n - first < kBlock ? (int)(n - first) : kBlock;
   const int W = (K + kChunk - 1) / kChunk;
-  stage_rows(points, first, rows, C, tile);
+  stage_rows<kBlock>(points, first, rows, C, tile);
   long long total;
   const long long start = block_exclusive_scan<long long>(t < K ? (long long)counts[t] : 0ll, wtot, &total);
   if (t < K) base[t] = start + block_offs[(size_t)t * blocks + blockIdx.x];

@@ -481,32 +481,10 @@ def descriptors(points, plans):
     return descs
 
 
-def paste_descriptors(plans, dev):
-    """(the bfhip_points_aug_paste_desc array of a batch, the device tensor it points into): every plan's pasted rows and plane
-    table packed into ONE pinned host buffer and uploaded with ONE non-blocking copy on the current stream."""
-    parts = [a.reshape(-1) for plan in plans if plan.paste_points is not None for a in (plan.paste_points, plan.paste_planes)]
-    host = torch.empty(sum(a.size for a in parts), dtype=torch.float32, pin_memory=True)
-    if host.numel():
-        np.concatenate(parts, out=host.numpy())
-    table = torch.empty(host.numel(), dtype=torch.float32, device=dev)
-    table.copy_(host, non_blocking=True)
-    descs, at, base = (_Paste * len(plans))(), 0, table.data_ptr()
-    for d, plan in zip(descs, plans):
-        if plan.paste_points is None:
-            d.points, d.n_points, d.planes, d.n_boxes = None, 0, None, 0
-            continue
-        m, k = plan.paste_points.shape[0], plan.paste_planes.shape[0]
-        d.points, d.n_points = (base + 4 * at if m else None), m
-        at += plan.paste_points.size
-        d.planes, d.n_boxes = (base + 4 * at if k else None), k
-        at += plan.paste_planes.size
-    return descs, table
-
-
-def sweep_descriptors(plans, dev):
-    """(the bfhip_points_aug_paste_desc array or None when no plan has a paste, the bfhip_points_aug_sweeps_desc array, the device
-    tensor both point into): paste_descriptors with the plans' segment tables in front of the paste data -- still ONE pinned
-    host buffer and ONE non-blocking copy on the current stream."""
+def table_descriptors(plans, dev):
+    """(the bfhip_points_aug_paste_desc array or None when no plan has a paste, the bfhip_points_aug_sweeps_desc array or None
+    when no plan has a sweep step, the device tensor both point into): the plans' segment tables, then every plan's pasted rows
+    and plane table, packed into ONE pinned host buffer and uploaded with ONE non-blocking copy on the current stream."""
     tables = [sweep_segments(plan) if plan.sweep_starts is not None else None for plan in plans]
     pasted = [plan for plan in plans if plan.paste_points is not None]
     parts = [t.view(np.uint8) for t in tables if t is not None]
@@ -516,37 +494,32 @@ def sweep_descriptors(plans, dev):
         np.concatenate(parts, out=host.numpy())
     table = torch.empty(host.numel(), dtype=torch.uint8, device=dev)  # the allocator's blocks are 512-byte aligned
     table.copy_(host, non_blocking=True)
-    sweeps, at, base = (_Sweeps * len(plans))(), 0, table.data_ptr()
-    for d, t, plan in zip(sweeps, tables, plans):
-        if t is None:
-            d.segments, d.n_segments = None, 0
-            continue
-        d.segments, d.n_segments = base + at, len(t)  # 112-byte entries from an aligned base: 8-byte aligned
-        d.first[:len(t) + 1] = [int(v) for v in plan.sweep_starts]
-        at += t.nbytes
-    if not pasted:
-        return None, sweeps, table
-    pastes = (_Paste * len(plans))()
-    for d, plan in zip(pastes, plans):
-        if plan.paste_points is None:
-            d.points, d.n_points, d.planes, d.n_boxes = None, 0, None, 0
-            continue
-        m, k = plan.paste_points.shape[0], plan.paste_planes.shape[0]
-        d.points, d.n_points = (base + at if m else None), m
-        at += plan.paste_points.nbytes
-        d.planes, d.n_boxes = (base + at if k else None), k
-        at += plan.paste_planes.nbytes
+    at, base = 0, table.data_ptr()  # byte offsets; a zero-initialised descriptor is an empty one
+    sweeps = (_Sweeps * len(plans))() if any(t is not None for t in tables) else None
+    for i, t in enumerate(tables):
+        if t is not None:
+            d = sweeps[i]
+            d.segments, d.n_segments = base + at, len(t)  # 112-byte entries in front, from an aligned base: 8-byte aligned
+            d.first[:len(t) + 1] = [int(v) for v in plans[i].sweep_starts]
+            at += t.nbytes
+    pastes = (_Paste * len(plans))() if pasted else None
+    for i, plan in enumerate(plans):
+        if plan.paste_points is not None:
+            d, m, k = pastes[i], plan.paste_points.shape[0], plan.paste_planes.shape[0]
+            d.points, d.n_points = (base + at if m else None), m
+            at += plan.paste_points.nbytes
+            d.planes, d.n_boxes = (base + at if k else None), k
+            at += plan.paste_planes.nbytes
     return pastes, sweeps, table
 
 
 def fused_points_aug(points, plans):
     """points: list of device float32 [n_i, C]; plans: list of PointsAugPlan -> the list of [kept_i, C] tensors, views of one
     buffer of sum(n_i + pasted rows of i) rows.  Three launches per 16 samples, then ONE host read per batch: the B kept counts,
-    which the views' shapes need (it waits for the launches).  Plans with a paste add one host-to-device copy per batch
-    (paste_descriptors) and go through bfhip_points_aug_paste; a batch without any takes bfhip_points_aug as before.  A batch
-    in which any plan has a sweep step goes through bfhip_points_aug_sweeps, its segment tables in that same one copy."""
+    which the views' shapes need (it waits for the launches).  Plans with a paste or a sweep step add one host-to-device copy per
+    batch (table_descriptors): a batch in which any plan has a sweep step goes through bfhip_points_aug_sweeps, otherwise one
+    with a paste through bfhip_points_aug_paste, and a batch with neither takes bfhip_points_aug, with no upload at all."""
     B, C, dev = len(points), int(points[0].shape[1]), points[0].device
-    pasted = any(plan.paste_points is not None for plan in plans)
     sizes = [int(p.shape[0]) + (len(plan.paste_points) if plan.paste_points is not None else 0) for p, plan in zip(points, plans)]
     total = sum(sizes)
     out = torch.empty((total, C), dtype=torch.float32, device=dev)
@@ -554,18 +527,16 @@ def fused_points_aug(points, plans):
     nbytes = _lib.call_size("bfhip_points_aug_workspace_bytes", total, B)
     work = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
     descs = descriptors(points, plans)
+    tail = (B, C, out.data_ptr() if total else None, kept.data_ptr(), work.data_ptr(), nbytes, _lib.stream_of(out))
     with torch.cuda.device(dev):
-        if any(plan.sweep_starts is not None for plan in plans):
-            pastes, sweeps, table = sweep_descriptors(plans, dev)  # `table` owns the device memory the descriptors point into
-            _lib.call("bfhip_points_aug_sweeps", descs, pastes, sweeps, B, C, out.data_ptr() if total else None, kept.data_ptr(),
-                      work.data_ptr(), nbytes, _lib.stream_of(out))
-        elif pasted:
-            pastes, table = paste_descriptors(plans, dev)  # `table` owns the device memory the descriptors point into
-            _lib.call("bfhip_points_aug_paste", descs, pastes, B, C, out.data_ptr() if total else None, kept.data_ptr(),
-                      work.data_ptr(), nbytes, _lib.stream_of(out))
+        if any(plan.paste_points is not None or plan.sweep_starts is not None for plan in plans):
+            pastes, sweeps, table = table_descriptors(plans, dev)  # `table` owns the device memory the descriptors point into
+            if sweeps is not None:
+                _lib.call("bfhip_points_aug_sweeps", descs, pastes, sweeps, *tail)
+            else:
+                _lib.call("bfhip_points_aug_paste", descs, pastes, *tail)
         else:
-            _lib.call("bfhip_points_aug", descs, B, C, out.data_ptr() if total else None, kept.data_ptr(), work.data_ptr(),
-                      nbytes, _lib.stream_of(out))
+            _lib.call("bfhip_points_aug", descs, *tail)
     counts = kept.cpu().tolist()  # the batch's one host read
     views, row = [], 0
     for n, k in zip(sizes, counts):

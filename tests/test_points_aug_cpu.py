@@ -303,6 +303,69 @@ def test_entry_point_rejects_bad_arguments_before_any_launch():
     assert not pa.fused_supported([torch.zeros(4, 5)]) and not pa.fused_supported([])
 
 
+def test_paste_and_sweeps_entries_reject_bad_arguments_before_any_launch():
+    """Host-side checks only, through the driver the three entries share: every call here returns before a launch.  The cases
+    are those of test_object_sample_gpu.py::test_invalid_arguments_are_rejected and of test_multi_sweep_gpu.py::
+    test_invalid_tables_are_rejected_and_nothing_is_launched, without their valid calls."""
+    lib = _lib.load()
+    kept = (ctypes.c_int32 * 1)()
+    fake = 4096  # never dereferenced
+    descs = (pa._Sample * 1)()
+    descs[0].points, descs[0].n = fake, 8
+
+    def paste(points=fake, n_points=8, planes=fake + 128, n_boxes=2, pastes=True, C=4, out=fake, bytes_=1 << 20, n_samples=1):
+        p = (pa._Paste * 1)()
+        p[0].points, p[0].n_points, p[0].planes, p[0].n_boxes = points, n_points, planes, n_boxes
+        return lib.bfhip_points_aug_paste(descs, p if pastes else None, n_samples, C, out, kept, fake, bytes_, None)
+
+    def sweeps(first=(0, 4, 8), n_segments=2, segments=fake, pastes=None, sweeps=True, C=5, out=fake, bytes_=1 << 20, n_samples=1):
+        w = (pa._Sweeps * 1)()
+        w[0].segments, w[0].n_segments = segments, n_segments
+        w[0].first[:len(first)] = list(first)
+        return lib.bfhip_points_aug_sweeps(descs, pastes, w if sweeps else None, n_samples, C, out, kept, fake, bytes_, None)
+
+    def rejected(entry, text, **kw):
+        assert entry(**kw) == -1, kw  # BFHIP_E_INVALID
+        msg = lib.bfhip_last_error().decode()
+        assert msg.startswith("points_aug_%s: " % entry.__name__) and text in msg, (kw, msg)
+
+    rejected(paste, "n_boxes=65 (0 .. 64)", n_boxes=65)
+    rejected(paste, "n_boxes=-1", n_boxes=-1)
+    rejected(paste, "n_points=-1", n_points=-1)
+    rejected(paste, "n_points=8 points=", points=None)
+    rejected(paste, "n_boxes=2 (0 .. 64) planes=", planes=None)
+    rejected(paste, "a required pointer is NULL", pastes=False)
+    rejected(paste, "not 4-byte aligned", points=fake + 2)
+    rejected(paste, "not 4-byte aligned", planes=fake + 1)
+    rejected(paste, "2 columns (3 .. 8)", C=2)
+    rejected(paste, "9 columns (3 .. 8)", C=9)
+    rejected(paste, "n_samples=0", n_samples=0)
+    rejected(paste, "out is NULL", out=None)
+    rejected(paste, "workspace of 0 bytes", bytes_=0)
+
+    rejected(sweeps, "boundary 2 (8) is below boundary 1 (9)", first=(0, 9, 8))
+    rejected(sweeps, "boundaries run from 0 to 7", first=(0, 4, 7))
+    rejected(sweeps, "boundaries run from 1 to 8", first=(1, 4, 8))
+    rejected(sweeps, "n_segments=17 (0 .. 16)", n_segments=17)
+    rejected(sweeps, "n_segments=-1", n_segments=-1)
+    rejected(sweeps, "n_segments=2 (0 .. 16) segments=", segments=None)
+    rejected(sweeps, "4 columns (5 .. 8", C=4)
+    rejected(sweeps, "4 columns (5 .. 8", C=4, n_segments=0, segments=None)  # even without a sweep step
+    rejected(sweeps, "9 columns (5 .. 8", C=9)
+    rejected(sweeps, "segments not 8-byte aligned", segments=fake + 4)
+    rejected(sweeps, "a required pointer is NULL", sweeps=False)
+    rejected(sweeps, "n_samples=0", n_samples=0)
+    rejected(sweeps, "out is NULL", out=None)
+    rejected(sweeps, "workspace of 0 bytes", bytes_=0)
+    # the sweeps entry with paste descriptors: the same paste checks, and the pasted rows count towards the 2^31 bound
+    p = (pa._Paste * 1)()
+    p[0].points, p[0].n_points, p[0].planes, p[0].n_boxes = fake, 8, fake + 128, 65
+    rejected(sweeps, "n_boxes=65 (0 .. 64)", pastes=p)
+    p[0].n_boxes, p[0].n_points = 2, 2 ** 31 - 8
+    rejected(sweeps, "2^31", pastes=p)
+    rejected(paste, "2^31", n_points=2 ** 31 - 8)
+
+
 def test_eager_shift_height_scales_the_named_column():
     pts = cases.golden()["points"].copy()
     np.random.seed(4)

@@ -112,6 +112,39 @@ def test_empty_batches_and_more_samples_than_one_launch_holds(dev):
         assert _same_bits(g, pa.torch_points_aug(p, plan)), i
 
 
+def test_the_three_entries_agree_on_a_batch_without_paste_or_sweeps(dev):
+    """One batch of 17 samples (one more than a launch holds) through bfhip_points_aug, bfhip_points_aug_paste with empty paste
+    descriptors, and bfhip_points_aug_sweeps with n_segments = 0 everywhere, without and with empty paste descriptors: the same
+    kept counts and the same bytes from all four, those of torch_points_aug."""
+    C, sizes = 5, [0, 1, 255, 256, 257, 513, 100, 0, 300, 64, 65, 511, 512, 2, 700, 31, 400]
+    B = len(sizes)
+    assert B == 17
+    rs = np.random.RandomState(17)
+    points = [torch.from_numpy(((rs.rand(n, C) - 0.5) * np.array([130, 130, 10, 1, 1])).astype(np.float32)) for n in sizes]
+    plans = [pa.PointsAugPlan().set_rts(_rot(0.2 * i - 1.0), [0.3, -0.1 * i, 0.2], 0.95 + 0.01 * i, "RTS" if i % 2 else "RST")
+             .set_flip(i % 2, i % 3 == 0).set_range(RANGE).set_shuffle(1000 + i) for i in range(B)]
+    want = [pa.torch_points_aug(p, plan) for p, plan in zip(points, plans)]
+    assert any(0 < len(w) < n for w, n in zip(want, sizes))  # the range drops some rows
+    on_dev = [p.to(dev) for p in points]
+    descs = pa.descriptors(on_dev, plans)
+    total = sum(sizes)
+    nbytes = _lib.call_size("bfhip_points_aug_workspace_bytes", total, B)
+    work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    routes = {"points_aug": lambda tail: _lib.call("bfhip_points_aug", descs, *tail),
+              "paste, empty": lambda tail: _lib.call("bfhip_points_aug_paste", descs, (pa._Paste * B)(), *tail),
+              "sweeps": lambda tail: _lib.call("bfhip_points_aug_sweeps", descs, None, (pa._Sweeps * B)(), *tail),
+              "sweeps + paste, empty": lambda tail: _lib.call("bfhip_points_aug_sweeps", descs, (pa._Paste * B)(), (pa._Sweeps * B)(), *tail)}
+    for name, route in routes.items():
+        out = torch.full((total, C), float("nan"), device=dev)
+        kept = torch.full((B,), -1, dtype=torch.int32, device=dev)
+        route((B, C, out.data_ptr(), kept.data_ptr(), work.data_ptr(), nbytes, _lib.stream_of(out)))
+        assert kept.tolist() == [len(w) for w in want], name
+        row = 0
+        for i, (n, w) in enumerate(zip(sizes, want)):
+            assert _same_bits(out[row:row + len(w)], w), (name, i)
+            row += n
+
+
 def test_golden_draws_through_the_kernel_path(dev):
     draws = list(range(cases.n_draws()))
     deferred = [cases.run(d, defer=True)[0] for d in draws]
