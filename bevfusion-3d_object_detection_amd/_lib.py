@@ -185,6 +185,18 @@ SIGNATURES = {
     "bfhip_detection_curves_workspace_bytes": (_c_sz, [ctypes.c_longlong, _c_int]),
     "bfhip_detection_curves": (_c_int, [_c_vp] * 5 + [ctypes.c_longlong, _c_int, _c_int, _c_int, _c_vp, _c_vp, ctypes.c_double,
                                         _c_int, ctypes.c_uint64] + [_c_vp] * 6 + [_c_vp, _c_sz, _c_vp]),
+    "bfhip_vis_max_dim": (_c_int, []),
+    "bfhip_vis_max_thickness": (_c_int, []),
+    "bfhip_vis_max_scale": (_c_int, []),
+    "bfhip_vis_workspace_bytes": (_c_sz, [_c_int, _c_int, _c_int]),
+    "bfhip_vis_camera_segments": (_c_int, [_c_vp, _c_int, _c_vp, _c_vp, _c_int, ctypes.c_float, _c_int, _c_int, _c_int, _c_vp, _c_sz,
+                                           _c_vp]),
+    "bfhip_vis_bev_segments": (_c_int, [_c_vp, _c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float, _c_int, _c_int, _c_int, _c_vp,
+                                        _c_sz, _c_vp]),
+    "bfhip_vis_composite": (_c_int, [_c_vp, _c_int, _c_int, _c_int, _c_vp, _c_sz, _c_int, _c_int, _c_vp, _c_vp, _c_int, _c_int, _c_int,
+                                     _c_vp, _c_vp]),
+    "bfhip_vis_bev_points": (_c_int, [_c_vp, ctypes.c_longlong, _c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float, _c_int, _c_vp,
+                                      _c_int, _c_int, _c_vp]),
 }
 
 

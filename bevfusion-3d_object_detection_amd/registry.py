@@ -52,6 +52,9 @@ TRANSFORMS = Registry("transforms")
 # evaluators (mmdet3d.registry.METRICS): NuScenesCustomMetric (evaluation.py), the `val_evaluator` of the reference's custom-data
 # configs -- the nuScenes detection protocol (matching, PR curves, mAP, the TP errors, NDS) on what predict() returns.
 METRICS = Registry("metrics")
+# what draws predictions (mmdet3d.registry.VISUALIZERS): PredictionVisualizer (visualize.py), the reference's two tools/visualize
+# scripts as one callable -- not mmengine's Det3DLocalVisualizer interface.
+VISUALIZERS = Registry("visualizers")
 
 
 def register(target):

@@ -1041,6 +1041,45 @@ int bfhip_detection_curves(const float *score, const int32_t *order, const int32
                            double *precision, double *confidence, double *err_curves, double *ap, double *tp_err,
                            int32_t *max_recall_ind, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Prediction visualiser (csrc/visualize.hip): 3D boxes drawn on the camera frames and tiled into a mosaic, and a bird's-eye
+ *   canvas of the cloud with the box footprints, as bevfusion_amd/visualize.py defines them bit for bit (the reference's
+ *   tools/visualize/visualize_bboxes_bevfusion.py and visualize_bev.py go through matplotlib).
+ *   table: float32 [n_boxes, 8]: x, y, z (bottom centre), dx, dy, dz, cos(yaw), sin(yaw); a row with a non-finite entry is not
+ *     drawn.  lidar2cam, cam2img: float32 [n_views, 3, 4], row-major.  thickness: 1/16 pixel, 1 .. bfhip_vis_max_thickness() =
+ *     2048.  Frames and canvases have 1 .. bfhip_vis_max_dim() = 8192 pixels a side.
+ *   bfhip_vis_camera_segments (one launch): one 32-byte record per (view, box, edge of the reference's 12) into the workspace:
+ *     corners, camera transform, clip against z_cam = near, projection and perspective divide in float32 (every operation
+ *     rounded once, none fused), ends in 1/16-pixel fixed point, clipped in int64 to a guard rectangle round the frame.  The
+ *     pixel box of every record is kept a second time, as a dense 8-byte array behind the records, for the composite's cull.
+ *   bfhip_vis_bev_segments (one launch): the same for the 4 footprint edges on a canvas with u = (x - x0) px_per_m,
+ *     v = (y1 - y) px_per_m (y1 the upper y limit: row 0 is the top).
+ *   bfhip_vis_composite (one launch): src uint8 [n_views, H, W, 3]; out uint8 [rows h, cols w, 3], h = H / scale, w = W / scale,
+ *     scale 1 .. bfhip_vis_max_scale() = 4.  Cell i of the rows x cols grid shows view cell_view[i] (int32 [rows cols]; outside
+ *     0 .. n_views - 1: black).  A source pixel whose centre lies within thickness / 2 of an edge (a capsule, exact in int64)
+ *     takes colors[box] (int32 [n_boxes]: r | g << 8 | b << 16) of the highest such box index; an output pixel is the rounded
+ *     mean (sum + scale^2 / 2) / scale^2 of its scale x scale source pixels.  n_boxes and edges (12 or 4) as given to the
+ *     segment call that filled the workspace; src and out must not overlap.
+ *   bfhip_vis_bev_points (one launch): points float32 [n, C], C >= 2; a point with 0 <= floor((x - x0) px_per_m) < W and
+ *     0 <= floor((y - y0) px_per_m) < H (y0 the lower limit; float32, a NaN fails) stores a white point_size x point_size
+ *     square round (col, H - 1 - that row), cut at the canvas, into canvas uint8 [H, W, 3], which the caller has zeroed.
+ *   The workspace, 256-byte aligned, has bfhip_vis_workspace_bytes(n_views, n_boxes, edges) bytes (n_views = 1 for the BEV).
+ *   No allocation, no synchronisation, no atomics: the same bytes on every run.  All pointers are device pointers.
+ * --------------------------------------------------------------------------------------- */
+int bfhip_vis_max_dim(void);
+int bfhip_vis_max_thickness(void);
+int bfhip_vis_max_scale(void);
+size_t bfhip_vis_workspace_bytes(int n_views, int n_boxes, int edges);
+int bfhip_vis_camera_segments(const float *table, int n_boxes, const float *lidar2cam, const float *cam2img, int n_views,
+                              float near, int thickness, int H, int W, void *workspace, size_t workspace_bytes, void *stream);
+int bfhip_vis_bev_segments(const float *table, int n_boxes, float x0, float y1, float px_per_m, int thickness, int H, int W,
+                           void *workspace, size_t workspace_bytes, void *stream);
+int bfhip_vis_composite(const uint8_t *src, int n_views, int H, int W, const void *workspace, size_t workspace_bytes, int n_boxes,
+                        int edges, const int32_t *colors, const int32_t *cell_view, int rows, int cols, int scale, uint8_t *out,
+                        void *stream);
+int bfhip_vis_bev_points(const float *points, long long n, int C, float x0, float y0, float px_per_m, int point_size,
+                         uint8_t *canvas, int H, int W, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
