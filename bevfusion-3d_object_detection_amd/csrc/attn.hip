@@ -23,7 +23,6 @@
 namespace bfhip {
 namespace {
 
-typedef unsigned short bf16_t;
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -36,12 +35,6 @@ constexpr int kChunk = 512;   // keys per workgroup (4 waves x 8 key tiles)
 // fp32 (2^-25) beside the largest weight of a row of up to 2^16 keys (>= 2^-16), with 2^-16 to spare for the spread of dA - D
 constexpr float kNegligible = -40.f;
 
-__device__ __forceinline__ float bf2f(bf16_t v) { return __uint_as_float((unsigned)v << 16); }
-__device__ __forceinline__ bf16_t f2bf(float f) {
-  unsigned u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (bf16_t)((u >> 16) | 0x40u);
-  return (bf16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
 __device__ __forceinline__ s16x4 ld4(const bf16_t *p) {  // 4 consecutive bf16 (8-byte aligned)
   uint2 u = *(const uint2 *)p;
   s16x4 r;
@@ -201,7 +194,7 @@ __global__ __launch_bounds__(256) void attn_out_kernel(const bf16_t *__restrict_
       for (int i = 0; i < 4; ++i) {
         float p = (kbase + i < dm.Lk && q < Lq) ? __expf(s[i] * dm.scale - lq_[t]) : 0.f;
         if (DROP) p = keep(seed, ((unsigned)bh * dm.Lq + q0 + q) * dm.Lk, kbase + i, dm.thresh24) ? p * dm.inv_keep : 0.f;
-        pa[i] = (short)f2bf(p);
+        pa[i] = (short)bf16_rne(p);
       }
       o[t] = MFMA16(pa, vb, o[t]);  // O[q = t*16 + lg*4 + i][dv = ln]
     }
@@ -235,7 +228,7 @@ __global__ __launch_bounds__(256) void attn_out_combine(const float *__restrict_
     a1 += opart[(((size_t)bh * dm.nchunk + c + 1) * dm.Lq + q) * kD + dv];
   }
   if (c < dm.nchunk) a0 += opart[(((size_t)bh * dm.nchunk + c) * dm.Lq + q) * kD + dv];
-  O[((size_t)b * dm.Lq + q) * dm.E + h * kD + dv] = f2bf(a0 + a1);
+  O[((size_t)b * dm.Lq + q) * dm.E + h * kD + dv] = (bf16_t)bf16_rne(a0 + a1);
 }
 
 // ---------------------------------------------------------------------------------------------------- backward
@@ -269,7 +262,7 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const bf16_t *__restrict_
     for (int j = 0; j < kD; ++j) {
       bf16_t qv = i < dm.Lq ? Qb[(size_t)i * dm.E + j] : (bf16_t)0, gv = i < dm.Lq ? dOb[(size_t)i * dm.E + j] : (bf16_t)0;
       qs[i][j] = qv; dos[i][j] = gv;
-      if (i < dm.Lq) acc += bf2f(gv) * bf2f(Ob[(size_t)i * dm.E + j]);
+      if (i < dm.Lq) acc += bf16_to_f32(gv) * bf16_to_f32(Ob[(size_t)i * dm.E + j]);
     }
     dsum[i] = acc;
     ls[i] = i < dm.Lq ? lse[(size_t)bh * dm.Lq + i] : 0.f;
@@ -322,11 +315,11 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const bf16_t *__restrict_
           da = kp ? da * dm.inv_keep : 0.f;
           a = kp ? p * dm.inv_keep : 0.f;
         }
-        const bf16_t dsv = f2bf(p * (da - dq1) * dm.scale);
+        const bf16_t dsv = (bf16_t)bf16_rne(p * (da - dq1) * dm.scale);
         dsa[i] = (short)dsv;
         // the same two tiles transposed (rows = keys) for the reductions over queries: through wave-private LDS
         tds[wave][lg * 4 + i][ln] = dsv;
-        tas[wave][lg * 4 + i][ln] = f2bf(a);
+        tas[wave][lg * 4 + i][ln] = (bf16_t)bf16_rne(a);
       }
       dq[t] = MFMA16(dsa, kcol, dq[t]);  // dQ[q = t*16 + lg*4 + i][d = ln]
       s16x4 qcol, gcol;  // B of dS^T Q / A^T dO: B[k = q lg*4 + j][n = d = ln]
@@ -344,8 +337,8 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const bf16_t *__restrict_
     for (int i = 0; i < 4; ++i) {
       const int kk = key0 + kt * 16 + lg * 4 + i;
       if (kk < dm.Lk) {
-        dK[((size_t)b * dm.Lk + kk) * dm.E + h * kD + ln] = f2bf(dk[i]);
-        dV[((size_t)b * dm.Lk + kk) * dm.E + h * kD + ln] = f2bf(dv[i]);
+        dK[((size_t)b * dm.Lk + kk) * dm.E + h * kD + ln] = (bf16_t)bf16_rne(dk[i]);
+        dV[((size_t)b * dm.Lk + kk) * dm.E + h * kD + ln] = (bf16_t)bf16_rne(dv[i]);
       }
     }
     __builtin_amdgcn_wave_barrier();

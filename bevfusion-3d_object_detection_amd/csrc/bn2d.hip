@@ -22,45 +22,48 @@
 namespace bfhip {
 namespace {
 
-typedef unsigned short bf16_t;
-
-template <typename T> struct Vec;
-template <> struct Vec<float> {
-  static constexpr int V = 4;
-  static __device__ __forceinline__ void load(const float *p, float *o) {
-    float4 v = *(const float4 *)p;
-    o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
-  }
-  static __device__ __forceinline__ void store(float *p, const float *o) { *(float4 *)p = make_float4(o[0], o[1], o[2], o[3]); }
-};
-template <> struct Vec<bf16_t> {
-  static constexpr int V = 8;
-  static __device__ __forceinline__ void load(const bf16_t *p, float *o) {
-    uint4 v = *(const uint4 *)p;
-    const unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      o[2 * i] = __uint_as_float(w[i] << 16);
-      o[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-    }
-  }
-  static __device__ __forceinline__ unsigned rne(float f) {  // fp32 -> bf16, round to nearest even (NaN kept quiet)
-    unsigned u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
-    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-  }
-  static __device__ __forceinline__ void store(bf16_t *p, const float *o) {
-    uint4 v;
-    v.x = rne(o[0]) | (rne(o[1]) << 16);
-    v.y = rne(o[2]) | (rne(o[3]) << 16);
-    v.z = rne(o[4]) | (rne(o[5]) << 16);
-    v.w = rne(o[6]) | (rne(o[7]) << 16);
-    *(uint4 *)p = v;
-  }
-};
-
 // A block covers Lb vector columns (Lb*V channels, column tile blockIdx.y) x R row lanes; blockIdx.x is the row slab.
 struct Map { int Lb, R, rpb; };  // vector columns per block, row lanes per block, rows per slab
+
+// What a thread owns: channel vector cv (channels [col, col + V)) and the rows r0 + rl, r0 + rl + R, ... below r1 of its slab.
+struct Lane {
+  int cv, rl;
+  bool live;
+  long long r0, r1;
+  size_t col;
+};
+template <int V>
+__device__ __forceinline__ Lane lane_of(const Map &mp, long long M, int C) {
+  const int t = threadIdx.x;
+  Lane ln;
+  ln.cv = blockIdx.y * mp.Lb + t % mp.Lb;
+  ln.rl = t / mp.Lb;
+  ln.live = ln.rl < mp.R && ln.cv * V < C;
+  ln.r0 = (long long)blockIdx.x * mp.rpb;
+  ln.r1 = ln.r0 + mp.rpb < M ? ln.r0 + mp.rpb : M;
+  ln.col = (size_t)ln.cv * V;
+  return ln;
+}
+
+// Walks the lane's rows U at a time, then the rest one by one.  load(r, row) only issues the loads of row r; use(r, row) does
+// the arithmetic and the stores.  All U loads go out before the first use: U rows in flight per thread.  The load step
+// captures by value (pointers and the lane only): with reference captures the compiler serialised the loads of one kernel.
+template <int U, typename Row, typename Load, typename Use>
+__device__ __forceinline__ void walk_rows(const Lane &ln, int R, Load load, Use use) {
+  long long r = ln.r0 + ln.rl;
+  for (; r + (long long)(U - 1) * R < ln.r1; r += (long long)U * R) {
+    Row row[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) load(r + (long long)u * R, row[u]);
+#pragma unroll
+    for (int u = 0; u < U; ++u) use(r + (long long)u * R, row[u]);
+  }
+  for (; r < ln.r1; r += R) {
+    Row row;
+    load(r, row);
+    use(r, row);
+  }
+}
 
 // Device-coherent accesses for the data that blocks hand to one another inside a launch (finish_in_last_block): agent-scope
 // relaxed atomics go to the coherence point themselves (sc1 loads / write-through stores), so no cache-wide release / acquire
@@ -89,14 +92,15 @@ __device__ __forceinline__ void combine_rows(const float *s0, const float *s1, i
   }
 }
 
-// ---- finalize inside the reduction launch -------------------------------------------------------------------------------
-// The per-channel finalisation (mean / invstd / affine coefficients, or dgamma / dbeta / dx coefficients) used to be a third
-// launch between the reduction and the elementwise pass: ~5 us of kernel plus a launch gap, 208 times per training step.
-// It now runs in the LAST-ARRIVING block of the reduction launch, as a two-level tree so that no block ever reads more than
-// 32 partial rows: the slabs of a column tile form groups of 32; the last block of a group to arrive adds the group's partial
-// rows (fp64, slab order) into gp[group]; the last group to finish adds the <= 32 group rows (group order) and finalises.
-// Sums are therefore in a fixed order whatever the arrival order (deterministic).  Arrival counters live in a small
-// zero-initialised, self-resetting buffer owned by the library, one per stream (kernels of one stream run in order).
+// ---- finalize inside the reduction launch (opt-in: BFHIP_BN2D_FOLD=1) ------------------------------------------------------
+// The per-channel finalisation (mean / invstd / affine coefficients, or dgamma / dbeta / dx coefficients) is a launch of its
+// own between the reduction and the elementwise pass (bn2d_finalize_kernel).  With BFHIP_BN2D_FOLD=1 it runs instead in the
+// LAST-ARRIVING block of the reduction launch; that measured slower, so it is off unless asked for.  It is a two-level tree so
+// that no block ever reads more than 32 partial rows: the slabs of a column tile form groups of 32; the last block of a group
+// to arrive adds the group's partial rows (fp64, slab order) into gp[group]; the last group to finish adds the <= 32 group
+// rows (group order) and finalises.  Sums are therefore in a fixed order whatever the arrival order (deterministic).  Arrival
+// counters live in a small zero-initialised, self-resetting buffer owned by the library, one per stream (kernels of one stream
+// run in order).
 constexpr int kGroup = 32;
 struct Tree {
   int *cnt;    // [column tile][1 + ng] arrival counters (all zero between launches)
@@ -108,7 +112,7 @@ template <typename Fin>
 __device__ __forceinline__ void finish_in_last_block(const float *__restrict__ partial, Tree tr, int C, int c0, int ncl,
                                                      Fin fin) {
   __shared__ int s_flag;
-  if (!tr.cnt) return;  // finalisation as a separate launch (BFHIP_BN2D_FOLD=0, A/B)
+  if (!tr.cnt) return;  // the default: finalisation is a separate launch
   const int t = threadIdx.x;
   const int g = blockIdx.x / kGroup;
   const int k0 = g * kGroup;
@@ -222,33 +226,20 @@ struct SumFin {
 template <typename T>
 __global__ __launch_bounds__(256) void bn2d_stats_kernel(const T *__restrict__ x, long long M, int C, Map mp,
                                                          float *__restrict__ partial, Tree tr, FwdFin fin) {
-  constexpr int V = Vec<T>::V;
+  constexpr int V = Vec16<T>::V;
   __shared__ float sm[2 * 256 * V];
-  const int t = threadIdx.x, cv = blockIdx.y * mp.Lb + t % mp.Lb, rl = t / mp.Lb;
-  const bool live = rl < mp.R && cv * V < C;
+  const Lane ln = lane_of<V>(mp, M, C);
   float s0[V], s1[V];
 #pragma unroll
   for (int j = 0; j < V; ++j) { s0[j] = 0.f; s1[j] = 0.f; }
-  if (live) {
-    const long long r0 = (long long)blockIdx.x * mp.rpb, r1 = r0 + mp.rpb < M ? r0 + mp.rpb : M;
-    const T *p = x + (size_t)cv * V;
-    long long r = r0 + rl;
-    for (; r + 3LL * mp.R < r1; r += 4LL * mp.R) {
-      float v[4][V];
+  struct Row { float v[V]; };
+  if (ln.live)
+    walk_rows<4, Row>(
+        ln, mp.R, [=](long long r, Row &w) { Vec16<T>::load(x + (size_t)r * C + ln.col, w.v); },
+        [&](long long, Row &w) {
 #pragma unroll
-      for (int u = 0; u < 4; ++u) Vec<T>::load(p + (size_t)(r + (long long)u * mp.R) * C, v[u]);
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int j = 0; j < V; ++j) { s0[j] += v[u][j]; s1[j] += v[u][j] * v[u][j]; }
-    }
-    for (; r < r1; r += mp.R) {
-      float v[V];
-      Vec<T>::load(p + (size_t)r * C, v);
-#pragma unroll
-      for (int j = 0; j < V; ++j) { s0[j] += v[j]; s1[j] += v[j] * v[j]; }
-    }
-  }
+          for (int j = 0; j < V; ++j) { s0[j] += w.v[j]; s1[j] += w.v[j] * w.v[j]; }
+        });
   combine_rows<V>(s0, s1, mp.Lb, mp.R, C, partial, sm);
   finish_in_last_block(partial, tr, C, blockIdx.y * mp.Lb * V, mp.Lb * V, fin);
 }
@@ -312,65 +303,60 @@ __global__ __launch_bounds__(256) void bn2d_apply_kernel(const T *__restrict__ x
                                                          T *__restrict__ y, unsigned char *__restrict__ relu_mask) {
   // relu_mask (optional, bf16 + residual + ReLU): one BIT per element, [M][C / 8] bytes -- what the backward needs of y (y > 0);
   // reading it instead of y saves two passes over the tensor per residual layer (bfhip_bn2d_bwd_mask)
-  constexpr int V = Vec<T>::V;
-  const int t = threadIdx.x, cv = blockIdx.y * mp.Lb + t % mp.Lb, rl = t / mp.Lb;
-  const bool live = rl < mp.R && cv * V < C;
-  if (!live) return;
+  constexpr int V = Vec16<T>::V;
+  const Lane ln = lane_of<V>(mp, M, C);
+  if (!ln.live) return;
   float a[V], b[V];
 #pragma unroll
-  for (int j = 0; j < V; ++j) { a[j] = stats[2 * C + cv * V + j]; b[j] = stats[3 * C + cv * V + j]; }
-  const long long r0 = (long long)blockIdx.x * mp.rpb, r1 = r0 + mp.rpb < M ? r0 + mp.rpb : M;
-  const size_t col = (size_t)cv * V;
-  long long r = r0 + rl;
-  for (; r + mp.R < r1; r += 2LL * mp.R) {
-    float v[2][V], q[2][V];
+  for (int j = 0; j < V; ++j) { a[j] = stats[2 * C + ln.cv * V + j]; b[j] = stats[3 * C + ln.cv * V + j]; }
+  struct Row { float v[V], q[V]; };
+  walk_rows<2, Row>(
+      ln, mp.R,
+      [=](long long r, Row &w) {
+        Vec16<T>::load(x + (size_t)r * C + ln.col, w.v);
+        if (RES) Vec16<T>::load(res + (size_t)r * C + ln.col, w.q);
+      },
+      [&](long long r, Row &w) {
+        unsigned bits = 0;
 #pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      Vec<T>::load(x + (size_t)(r + (long long)u * mp.R) * C + col, v[u]);
-      if (RES) Vec<T>::load(res + (size_t)(r + (long long)u * mp.R) * C + col, q[u]);
-    }
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      unsigned bits = 0;
-#pragma unroll
-      for (int j = 0; j < V; ++j) {
-        float o = v[u][j] * a[j] + b[j];
-        if (RES) o += q[u][j];
-        if (o > 0.f) bits |= 1u << j;
-        v[u][j] = (RELU && !(o > 0.f)) ? 0.f : o;
-      }
-      Vec<T>::store(y + (size_t)(r + (long long)u * mp.R) * C + col, v[u]);
-      if (V == 8 && relu_mask) relu_mask[(size_t)(r + (long long)u * mp.R) * (C >> 3) + cv] = (unsigned char)bits;
-    }
-  }
-  for (; r < r1; r += mp.R) {
-    float v[V], q[V];
-    Vec<T>::load(x + (size_t)r * C + col, v);
-    if (RES) Vec<T>::load(res + (size_t)r * C + col, q);
-    unsigned bits = 0;
-#pragma unroll
-    for (int j = 0; j < V; ++j) {
-      float o = v[j] * a[j] + b[j];
-      if (RES) o += q[j];
-      if (o > 0.f) bits |= 1u << j;
-      v[j] = (RELU && !(o > 0.f)) ? 0.f : o;
-    }
-    Vec<T>::store(y + (size_t)r * C + col, v);
-    if (V == 8 && relu_mask) relu_mask[(size_t)r * (C >> 3) + cv] = (unsigned char)bits;
-  }
+        for (int j = 0; j < V; ++j) {
+          float o = w.v[j] * a[j] + b[j];
+          if (RES) o += w.q[j];
+          if (o > 0.f) bits |= 1u << j;
+          w.v[j] = (RELU && !(o > 0.f)) ? 0.f : o;
+        }
+        Vec16<T>::store(y + (size_t)r * C + ln.col, w.v);
+        if (V == 8 && relu_mask) relu_mask[(size_t)r * (C >> 3) + ln.cv] = (unsigned char)bits;
+      });
 }
 
+// One row of the backward: the incoming gradient, x and what the ReLU mask is taken from.
 // MASK: 0 = no ReLU, 1 = ReLU mask recomputed from x (a*x + b > 0), 2 = ReLU mask from the saved output y, 3 = from the bit mask
-// the forward stored (yv[0] carries the byte of this 8-channel vector)
+// the forward stored (bits: the byte of this 8-channel vector)
+template <typename T> struct GradRow {
+  float g[Vec16<T>::V], xv[Vec16<T>::V], yv[Vec16<T>::V];
+  unsigned bits;
+};
+
 template <typename T, int MASK>
-__device__ __forceinline__ void masked_grad(float *g, const float *xv, const float *yv, const float *a, const float *b) {
-  constexpr int V = Vec<T>::V;
-  const unsigned bits = MASK == 3 ? __float_as_uint(yv[0]) : 0u;
+__device__ __forceinline__ void load_grad_row(const T *dy, const T *x, const T *y, long long r, int C, const Lane &ln,
+                                              GradRow<T> &w) {
+  const size_t off = (size_t)r * C + ln.col;
+  Vec16<T>::load(dy + off, w.g);
+  Vec16<T>::load(x + off, w.xv);
+  if (MASK == 2) Vec16<T>::load(y + off, w.yv);
+  if (MASK == 3) w.bits = ((const unsigned char *)y)[(size_t)r * (C >> 3) + ln.cv];
+}
+
+// g = dy * [y > 0]
+template <typename T, int MASK>
+__device__ __forceinline__ void masked_grad(GradRow<T> &w, const float *a, const float *b) {
+  constexpr int V = Vec16<T>::V;
 #pragma unroll
   for (int j = 0; j < V; ++j) {
-    if (MASK == 1 && !(xv[j] * a[j] + b[j] > 0.f)) g[j] = 0.f;
-    if (MASK == 2 && !(yv[j] > 0.f)) g[j] = 0.f;
-    if (MASK == 3 && !((bits >> j) & 1u)) g[j] = 0.f;
+    if (MASK == 1 && !(w.xv[j] * a[j] + b[j] > 0.f)) w.g[j] = 0.f;
+    if (MASK == 2 && !(w.yv[j] > 0.f)) w.g[j] = 0.f;
+    if (MASK == 3 && !((w.bits >> j) & 1u)) w.g[j] = 0.f;
   }
 }
 
@@ -380,52 +366,27 @@ __global__ __launch_bounds__(256) void bn2d_bwd_reduce_kernel(const T *__restric
                                                               const T *__restrict__ y,
                                                               const float *__restrict__ stats, long long M, int C,
                                                               Map mp, float *__restrict__ partial, Tree tr, BwdFin fin) {
-  constexpr int V = Vec<T>::V;
+  constexpr int V = Vec16<T>::V;
   __shared__ float sm[2 * 256 * V];
-  const int t = threadIdx.x, cv = blockIdx.y * mp.Lb + t % mp.Lb, rl = t / mp.Lb;
-  const bool live = rl < mp.R && cv * V < C;
+  const Lane ln = lane_of<V>(mp, M, C);
   float s0[V], s1[V];
 #pragma unroll
   for (int j = 0; j < V; ++j) { s0[j] = 0.f; s1[j] = 0.f; }
-  if (live) {
+  if (ln.live) {
     float mean[V], a[V], b[V];
 #pragma unroll
     for (int j = 0; j < V; ++j) {
-      mean[j] = stats[cv * V + j];
-      a[j] = stats[2 * C + cv * V + j];
-      b[j] = stats[3 * C + cv * V + j];
+      mean[j] = stats[ln.cv * V + j];
+      a[j] = stats[2 * C + ln.cv * V + j];
+      b[j] = stats[3 * C + ln.cv * V + j];
     }
-    const long long r0 = (long long)blockIdx.x * mp.rpb, r1 = r0 + mp.rpb < M ? r0 + mp.rpb : M;
-    const size_t col = (size_t)cv * V;
-    long long r = r0 + rl;
-    for (; r + mp.R < r1; r += 2LL * mp.R) {
-      float g[2][V], xv[2][V], yv[2][V];
+    walk_rows<2, GradRow<T>>(
+        ln, mp.R, [=](long long r, GradRow<T> &w) { load_grad_row<T, MASK>(dy, x, y, r, C, ln, w); },
+        [&](long long, GradRow<T> &w) {
+          masked_grad<T, MASK>(w, a, b);
 #pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        size_t off = (size_t)(r + (long long)u * mp.R) * C + col;
-        Vec<T>::load(dy + off, g[u]);
-        Vec<T>::load(x + off, xv[u]);
-        if (MASK == 2) Vec<T>::load(y + off, yv[u]);
-        if (MASK == 3) yv[u][0] = __uint_as_float(((const unsigned char *)y)[(size_t)(r + (long long)u * mp.R) * (C >> 3) + cv]);
-      }
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        masked_grad<T, MASK>(g[u], xv[u], yv[u], a, b);
-#pragma unroll
-        for (int j = 0; j < V; ++j) { s0[j] += g[u][j]; s1[j] += g[u][j] * (xv[u][j] - mean[j]); }
-      }
-    }
-    for (; r < r1; r += mp.R) {
-      float g[V], xv[V], yv[V];
-      size_t off = (size_t)r * C + col;
-      Vec<T>::load(dy + off, g);
-      Vec<T>::load(x + off, xv);
-      if (MASK == 2) Vec<T>::load(y + off, yv);
-      if (MASK == 3) yv[0] = __uint_as_float(((const unsigned char *)y)[(size_t)r * (C >> 3) + cv]);
-      masked_grad<T, MASK>(g, xv, yv, a, b);
-#pragma unroll
-      for (int j = 0; j < V; ++j) { s0[j] += g[j]; s1[j] += g[j] * (xv[j] - mean[j]); }
-    }
+          for (int j = 0; j < V; ++j) { s0[j] += w.g[j]; s1[j] += w.g[j] * (w.xv[j] - mean[j]); }
+        });
   }
   combine_rows<V>(s0, s1, mp.Lb, mp.R, C, partial, sm);
   finish_in_last_block(partial, tr, C, blockIdx.y * mp.Lb * V, mp.Lb * V, fin);
@@ -437,58 +398,29 @@ __global__ __launch_bounds__(256) void bn2d_bwd_apply_kernel(const T *__restrict
                                                              const float *__restrict__ stats,
                                                              const float *__restrict__ coef, long long M, int C,
                                                              Map mp, T *__restrict__ dx, T *__restrict__ dres) {
-  constexpr int V = Vec<T>::V;
-  const int t = threadIdx.x, cv = blockIdx.y * mp.Lb + t % mp.Lb, rl = t / mp.Lb;
-  const bool live = rl < mp.R && cv * V < C;
-  if (!live) return;
+  constexpr int V = Vec16<T>::V;
+  const Lane ln = lane_of<V>(mp, M, C);
+  if (!ln.live) return;
   float a[V], b[V], c1[V], c2[V], c3[V];
 #pragma unroll
   for (int j = 0; j < V; ++j) {
-    a[j] = stats[2 * C + cv * V + j];
-    b[j] = stats[3 * C + cv * V + j];
-    c1[j] = coef[cv * V + j];
-    c2[j] = coef[C + cv * V + j];
-    c3[j] = coef[2 * C + cv * V + j];
+    a[j] = stats[2 * C + ln.cv * V + j];
+    b[j] = stats[3 * C + ln.cv * V + j];
+    c1[j] = coef[ln.cv * V + j];
+    c2[j] = coef[C + ln.cv * V + j];
+    c3[j] = coef[2 * C + ln.cv * V + j];
   }
-  const long long r0 = (long long)blockIdx.x * mp.rpb, r1 = r0 + mp.rpb < M ? r0 + mp.rpb : M;
-  const size_t col = (size_t)cv * V;
-  long long r = r0 + rl;
-  for (; r + mp.R < r1; r += 2LL * mp.R) {
-    float g[2][V], xv[2][V], yv[2][V];
+  walk_rows<2, GradRow<T>>(
+      ln, mp.R, [=](long long r, GradRow<T> &w) { load_grad_row<T, MASK>(dy, x, y, r, C, ln, w); },
+      [&](long long r, GradRow<T> &w) {
+        const size_t off = (size_t)r * C + ln.col;
+        masked_grad<T, MASK>(w, a, b);
+        if (DRES) Vec16<T>::store(dres + off, w.g);
 #pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      size_t off = (size_t)(r + (long long)u * mp.R) * C + col;
-      Vec<T>::load(dy + off, g[u]);
-      Vec<T>::load(x + off, xv[u]);
-      if (MASK == 2) Vec<T>::load(y + off, yv[u]);
-      if (MASK == 3) yv[u][0] = __uint_as_float(((const unsigned char *)y)[(size_t)(r + (long long)u * mp.R) * (C >> 3) + cv]);
-    }
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      size_t off = (size_t)(r + (long long)u * mp.R) * C + col;
-      masked_grad<T, MASK>(g[u], xv[u], yv[u], a, b);
-      if (DRES) Vec<T>::store(dres + off, g[u]);
-#pragma unroll
-      for (int j = 0; j < V; ++j) xv[u][j] = c1[j] * g[u][j] + c2[j] * xv[u][j] + c3[j];
-      Vec<T>::store(dx + off, xv[u]);
-    }
-  }
-  for (; r < r1; r += mp.R) {
-    float g[V], xv[V], yv[V];
-    size_t off = (size_t)r * C + col;
-    Vec<T>::load(dy + off, g);
-    Vec<T>::load(x + off, xv);
-    if (MASK == 2) Vec<T>::load(y + off, yv);
-    if (MASK == 3) yv[0] = __uint_as_float(((const unsigned char *)y)[(size_t)r * (C >> 3) + cv]);
-    masked_grad<T, MASK>(g, xv, yv, a, b);
-    if (DRES) Vec<T>::store(dres + off, g);
-#pragma unroll
-    for (int j = 0; j < V; ++j) xv[j] = c1[j] * g[j] + c2[j] * xv[j] + c3[j];
-    Vec<T>::store(dx + off, xv);
-  }
+        for (int j = 0; j < V; ++j) w.xv[j] = c1[j] * w.g[j] + c2[j] * w.xv[j] + c3[j];
+        Vec16<T>::store(dx + off, w.xv);
+      });
 }
-
-inline int elem_size(int dtype) { return dtype == 1 ? 2 : 4; }
 
 // C must be a multiple of the 16-byte vector
 inline bool shape_ok(long long M, int C, int dtype) {
@@ -600,6 +532,13 @@ inline size_t plan_bytes(long long M, int C, int dtype, Plan *pl, void *workspac
   return off;
 }
 
+inline void launch_stats(const void *x, long long M, int C, int dtype, const Plan &pl, Tree tr, FwdFin fin, hipStream_t s) {
+  if (dtype == 1)
+    hipLaunchKernelGGL(bn2d_stats_kernel<bf16_t>, pl.grid, dim3(256), 0, s, (const bf16_t *)x, M, C, pl.mp, pl.partial, tr, fin);
+  else
+    hipLaunchKernelGGL(bn2d_stats_kernel<float>, pl.grid, dim3(256), 0, s, (const float *)x, M, C, pl.mp, pl.partial, tr, fin);
+}
+
 }  // namespace
 }  // namespace bfhip
 
@@ -621,16 +560,12 @@ BFHIP_EXPORT int bfhip_colsum(const void *x, long long M, int C, int dtype, floa
                               void *stream_) {
   hipStream_t s = (hipStream_t)stream_;
   BFHIP_REQUIRE(bfhip_bn2d_supported(M, C, dtype), "colsum: unsupported shape M=%lld C=%d dtype=%d", M, C, dtype);
-  BFHIP_REQUIRE(x && out && ((uintptr_t)x % 16) == 0, "colsum: null or misaligned pointer");
+  BFHIP_REQUIRE(x && out && aligned16(x), "colsum: null or misaligned pointer");
   BFHIP_REQUIRE_WORKSPACE(workspace, workspace_bytes, bfhip_bn2d_workspace_bytes(M, C, dtype), "colsum");
   Plan pl;
   plan_bytes(M, C, dtype, &pl, workspace);
   Tree tr{nullptr, pl.gp, pl.nblk, pl.ng};
-  FwdFin none{};
-  if (dtype == 1)
-    hipLaunchKernelGGL(bn2d_stats_kernel<bf16_t>, pl.grid, dim3(256), 0, s, (const bf16_t *)x, M, C, pl.mp, pl.partial, tr, none);
-  else
-    hipLaunchKernelGGL(bn2d_stats_kernel<float>, pl.grid, dim3(256), 0, s, (const float *)x, M, C, pl.mp, pl.partial, tr, none);
+  launch_stats(x, M, C, dtype, pl, tr, FwdFin{}, s);
   hipLaunchKernelGGL(bn2d_finalize_kernel<SumFin>, dim3(ceil_div(C, 8)), dim3(kFinThreads), 0, s, pl.partial, pl.nblk, SumFin{C, out});
   return check_launch("colsum");
 }
@@ -642,7 +577,7 @@ BFHIP_EXPORT int bfhip_bn2d_fwd(const void *x, const void *residual, const float
   hipStream_t s = (hipStream_t)stream_;
   BFHIP_REQUIRE(bfhip_bn2d_supported(M, C, dtype), "bn2d_fwd: unsupported shape M=%lld C=%d dtype=%d", M, C, dtype);
   BFHIP_REQUIRE(x && gamma && beta && stats && y, "bn2d_fwd: null pointer");
-  BFHIP_REQUIRE(((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 16) == 0 && ((uintptr_t)residual % 16) == 0,
+  BFHIP_REQUIRE(aligned16(x) && aligned16(y) && aligned16(residual),
                 "bn2d_fwd: tensors must be 16-byte aligned");
   BFHIP_REQUIRE_WORKSPACE(workspace, workspace_bytes, bfhip_bn2d_workspace_bytes(M, C, dtype), "bn2d_fwd");
   Plan pl;
@@ -654,10 +589,7 @@ BFHIP_EXPORT int bfhip_bn2d_fwd(const void *x, const void *residual, const float
   FwdFin fin{M, m_dev, C, eps, momentum, gamma, beta, stats, running_mean, running_var};
   ProfScope ps;
   prof_begin(BFHIP_OP_BN2D_FWD, s, &ps);
-  if (dtype == 1)
-    hipLaunchKernelGGL(bn2d_stats_kernel<bf16_t>, pl.grid, dim3(256), 0, s, (const bf16_t *)x, M, C, pl.mp, pl.partial, tr, fin);
-  else
-    hipLaunchKernelGGL(bn2d_stats_kernel<float>, pl.grid, dim3(256), 0, s, (const float *)x, M, C, pl.mp, pl.partial, tr, fin);
+  launch_stats(x, M, C, dtype, pl, tr, fin, s);
   if (!cnt) hipLaunchKernelGGL(bn2d_finalize_kernel<FwdFin>, dim3(ceil_div(C, 8)), dim3(kFinThreads), 0, s, pl.partial, pl.nblk, fin);
   if (dtype == 1) run_fwd<bf16_t>(x, residual, stats, M, C, pl.mp, pl.grid, relu, y, s);
   else run_fwd<float>(x, residual, stats, M, C, pl.mp, pl.grid, relu, y, s);
@@ -673,7 +605,7 @@ static int bn2d_fwd_partials_impl(const void *x, const void *residual, const flo
   BFHIP_REQUIRE(!relu_mask || (dtype == 1 && relu && residual), "bn2d_fwd_partials: a ReLU bit mask needs bf16 + residual + ReLU");
   BFHIP_REQUIRE(bfhip_bn2d_supported(M, C, dtype), "bn2d_fwd_partials: unsupported shape M=%lld C=%d dtype=%d", M, C, dtype);
   BFHIP_REQUIRE(x && gamma && beta && stats && y && partial && nblk > 0, "bn2d_fwd_partials: null pointer");
-  BFHIP_REQUIRE(((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 16) == 0 && ((uintptr_t)residual % 16) == 0,
+  BFHIP_REQUIRE(aligned16(x) && aligned16(y) && aligned16(residual),
                 "bn2d_fwd_partials: tensors must be 16-byte aligned");
   dim3 grid;
   Map mp = make_map(M, C, dtype, &grid);
@@ -715,8 +647,8 @@ static int bn2d_bwd_impl(const void *dy, const void *x, const void *y, const uns
   if (relu_mask) y = relu_mask;  // the kernels' MASK == 3 mode reads the bits through the y pointer
   BFHIP_REQUIRE(bfhip_bn2d_supported(M, C, dtype), "bn2d_bwd: unsupported shape M=%lld C=%d dtype=%d", M, C, dtype);
   BFHIP_REQUIRE(dy && x && stats && gamma && dx && dgb, "bn2d_bwd: null pointer");
-  BFHIP_REQUIRE(((uintptr_t)dy % 16) == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)dx % 16) == 0 &&
-                    ((uintptr_t)y % 16) == 0 && ((uintptr_t)dres % 16) == 0, "bn2d_bwd: tensors must be 16-byte aligned");
+  BFHIP_REQUIRE(aligned16(dy) && aligned16(x) && aligned16(dx) && aligned16(y) && aligned16(dres),
+                "bn2d_bwd: tensors must be 16-byte aligned");
   BFHIP_REQUIRE_WORKSPACE(workspace, workspace_bytes, bfhip_bn2d_workspace_bytes(M, C, dtype), "bn2d_bwd");
   Plan pl;
   plan_bytes(M, C, dtype, &pl, workspace);

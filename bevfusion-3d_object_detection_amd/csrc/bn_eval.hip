@@ -19,47 +19,10 @@
 namespace bfhip {
 namespace {
 
-typedef unsigned short bf16_t;
-
 constexpr int kBlock = 256;
 constexpr int kMaxVec = 512;     // vectors per row: one thread each, in column tiles of kBlock
 constexpr int kMaxBlocks = 2048;
 constexpr int kMinIters = 4;     // row groups per workgroup before the grid grows
-
-template <typename T> struct Vec;
-template <> struct Vec<float> {
-  static constexpr int V = 4;
-  static __device__ __forceinline__ void load(const float *p, float *o) {
-    const float4 v = *(const float4 *)p;
-    o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
-  }
-  static __device__ __forceinline__ void store(float *p, const float *o) { *(float4 *)p = make_float4(o[0], o[1], o[2], o[3]); }
-};
-template <> struct Vec<bf16_t> {
-  static constexpr int V = 8;
-  static __device__ __forceinline__ void load(const bf16_t *p, float *o) {
-    const uint4 v = *(const uint4 *)p;
-    const unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      o[2 * i] = __uint_as_float(w[i] << 16);
-      o[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-    }
-  }
-  static __device__ __forceinline__ unsigned rne(float f) {  // fp32 -> bf16, round to nearest even (NaN kept quiet)
-    const unsigned u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
-    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-  }
-  static __device__ __forceinline__ void store(bf16_t *p, const float *o) {
-    uint4 v;
-    v.x = rne(o[0]) | (rne(o[1]) << 16);
-    v.y = rne(o[2]) | (rne(o[3]) << 16);
-    v.z = rne(o[4]) | (rne(o[5]) << 16);
-    v.w = rne(o[6]) | (rne(o[7]) << 16);
-    *(uint4 *)p = v;
-  }
-};
 
 // V consecutive f32 parameters starting at channel c (a multiple of V; the base is 16-byte aligned)
 template <int V>
@@ -76,66 +39,83 @@ struct Shape {
   int C, L, Lb, R;      // channels; vectors per row; vectors per column tile (blockIdx.y); rows per workgroup iteration
 };
 
+// What a thread owns: channel vector cv (channels [col, col + V)) and row lane rl of every row group its workgroup walks.
+struct Lane {
+  int cv, rl;
+  bool live;
+  size_t col;
+};
+template <int V>
+__device__ __forceinline__ Lane lane_of(const Shape &sh) {
+  const int t = threadIdx.x;
+  Lane ln;
+  ln.cv = blockIdx.y * sh.Lb + t % sh.Lb;
+  ln.rl = t / sh.Lb;
+  ln.live = ln.rl < sh.R && ln.cv < sh.L;
+  ln.col = (size_t)ln.cv * V;
+  return ln;
+}
+
+// Walks the workgroup's row groups (grid stride) two at a time, then the odd one.  load(o, row) only issues the loads of the
+// row at element offset o; use(o, row, keep) does the arithmetic and stores if keep.  Both loads go out before the first use.
+// Only the LAST group can be short: a second row beyond M is loaded from the first row's address instead (a predicated load
+// is a branch the compiler will not issue loads across) and its result is dropped.
+template <typename Row, typename Load, typename Use>
+__device__ __forceinline__ void walk_groups(const Shape &sh, const Lane &ln, Load load, Use use) {
+  const long long step = gridDim.x;
+  long long g = blockIdx.x;
+  for (; g + step < sh.groups; g += 2 * step) {
+    const long long r0 = g * sh.R + ln.rl, r1 = (g + step) * sh.R + ln.rl;  // r0 < M
+    const bool ok1 = r1 < sh.M;
+    const size_t o0 = (size_t)r0 * sh.C + ln.col, o1 = (size_t)(ok1 ? r1 : r0) * sh.C + ln.col;
+    Row row[2];
+    load(o0, row[0]);
+    load(o1, row[1]);
+    use(o0, row[0], true);
+    use(o1, row[1], ok1);
+  }
+  if (g < sh.groups && g * sh.R + ln.rl < sh.M) {
+    const size_t o0 = (size_t)(g * sh.R + ln.rl) * sh.C + ln.col;
+    Row row;
+    load(o0, row);
+    use(o0, row, true);
+  }
+}
+
 template <typename T, bool RES, bool RELU>
 __global__ __launch_bounds__(kBlock) void bn_eval_fwd_kernel(const T *__restrict__ x, const T *__restrict__ res,
                                                              const float *__restrict__ gamma, const float *__restrict__ beta,
                                                              const float *__restrict__ rmean, const float *__restrict__ rvar,
                                                              float eps, Shape sh, T *__restrict__ y) {
-  constexpr int V = Vec<T>::V;
-  const int t = threadIdx.x, cv = blockIdx.y * sh.Lb + t % sh.Lb, rl = t / sh.Lb;
-  if (rl >= sh.R || cv >= sh.L) return;
+  constexpr int V = Vec16<T>::V;
+  const Lane ln = lane_of<V>(sh);
+  if (!ln.live) return;
   float a[V], mean[V], b[V];
   {
     float var[V];
-    load_param<V>(gamma, cv * V, a);
-    load_param<V>(rvar, cv * V, var);
-    load_param<V>(rmean, cv * V, mean);
-    load_param<V>(beta, cv * V, b);
+    load_param<V>(gamma, ln.cv * V, a);
+    load_param<V>(rvar, ln.cv * V, var);
+    load_param<V>(rmean, ln.cv * V, mean);
+    load_param<V>(beta, ln.cv * V, b);
 #pragma unroll
     for (int j = 0; j < V; ++j) a[j] *= 1.f / sqrtf(var[j] + eps);
   }
-  const size_t col = (size_t)cv * V;
-  const long long step = gridDim.x;
-  long long g = blockIdx.x;
-  // two row groups in flight per thread
-  for (; g + step < sh.groups; g += 2 * step) {
-    const long long r0 = g * sh.R + rl, r1 = (g + step) * sh.R + rl;  // r0 < M: only the LAST group can be short
-    const bool ok1 = r1 < sh.M;
-    const size_t o0 = (size_t)r0 * sh.C + col, o1 = (size_t)(ok1 ? r1 : r0) * sh.C + col;
-    float v[2][V], q[2][V];
-    Vec<T>::load(x + o0, v[0]);
-    Vec<T>::load(x + o1, v[1]);
-    if (RES) {
-      Vec<T>::load(res + o0, q[0]);
-      Vec<T>::load(res + o1, q[1]);
-    }
+  struct Row { float v[V], q[V]; };
+  walk_groups<Row>(
+      sh, ln,
+      [=](size_t o, Row &w) {
+        Vec16<T>::load(x + o, w.v);
+        if (RES) Vec16<T>::load(res + o, w.q);
+      },
+      [&](size_t o, Row &w, bool keep) {
 #pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-      for (int j = 0; j < V; ++j) {
-        float o = fmaf(v[u][j] - mean[j], a[j], b[j]);
-        if (RES) o += q[u][j];
-        v[u][j] = (RELU && !(o > 0.f)) ? 0.f : o;
-      }
-    Vec<T>::store(y + o0, v[0]);
-    if (ok1) Vec<T>::store(y + o1, v[1]);
-  }
-  if (g < sh.groups) {
-    const long long r = g * sh.R + rl;
-    if (r < sh.M) {
-      const size_t o0 = (size_t)r * sh.C + col;
-      float v[V], q[V];
-      Vec<T>::load(x + o0, v);
-      if (RES) Vec<T>::load(res + o0, q);
-#pragma unroll
-      for (int j = 0; j < V; ++j) {
-        float o = fmaf(v[j] - mean[j], a[j], b[j]);
-        if (RES) o += q[j];
-        v[j] = (RELU && !(o > 0.f)) ? 0.f : o;
-      }
-      Vec<T>::store(y + o0, v);
-    }
-  }
+        for (int j = 0; j < V; ++j) {
+          float r = fmaf(w.v[j] - mean[j], a[j], b[j]);
+          if (RES) r += w.q[j];
+          w.v[j] = (RELU && !(r > 0.f)) ? 0.f : r;
+        }
+        if (keep) Vec16<T>::store(y + o, w.v);
+      });
 }
 
 // dx and dres are written where their pointer is given (uniform over the launch).  AFF: also accumulate this workgroup's
@@ -146,43 +126,43 @@ __global__ __launch_bounds__(kBlock) void bn_eval_bwd_kernel(const T *__restrict
                                                              const float *__restrict__ rmean, const float *__restrict__ rvar,
                                                              float eps, Shape sh, T *__restrict__ dx, T *__restrict__ dres,
                                                              float *__restrict__ partial) {
-  constexpr int V = Vec<T>::V;
+  constexpr int V = Vec16<T>::V;
   __shared__ float sm[AFF ? 2 * kBlock * V : 1];
-  const int t = threadIdx.x, cv = blockIdx.y * sh.Lb + t % sh.Lb, rl = t / sh.Lb;
-  const bool live = rl < sh.R && cv < sh.L;
+  const int t = threadIdx.x;
+  const Lane ln = lane_of<V>(sh);
   float s0[V], s1[V];
 #pragma unroll
   for (int j = 0; j < V; ++j) s0[j] = s1[j] = 0.f;
-  if (live) {
+  if (ln.live) {
     float a[V], mean[V], rstd[V];
 #pragma unroll
     for (int j = 0; j < V; ++j) a[j] = mean[j] = rstd[j] = 0.f;
     if (dx || AFF) {
-      load_param<V>(rvar, cv * V, rstd);
+      load_param<V>(rvar, ln.cv * V, rstd);
 #pragma unroll
       for (int j = 0; j < V; ++j) rstd[j] = 1.f / sqrtf(rstd[j] + eps);
     }
     if (dx) {
-      load_param<V>(gamma, cv * V, a);
+      load_param<V>(gamma, ln.cv * V, a);
 #pragma unroll
       for (int j = 0; j < V; ++j) a[j] *= rstd[j];
     }
-    if (AFF) load_param<V>(rmean, cv * V, mean);
-    const size_t col = (size_t)cv * V;
+    if (AFF) load_param<V>(rmean, ln.cv * V, mean);
+    const size_t col = (size_t)ln.cv * V;
     for (long long g = blockIdx.x; g < sh.groups; g += gridDim.x) {
-      const long long r = g * sh.R + rl;
+      const long long r = g * sh.R + ln.rl;
       if (r >= sh.M) break;  // only the last group can be short
-      const size_t o = (size_t)r * sh.C + col;
+      const size_t o = (size_t)r * sh.C + ln.col;
       float gv[V], yv[V], xv[V];
-      Vec<T>::load(dy + o, gv);
-      if (RELU) Vec<T>::load(y + o, yv);
-      if (AFF) Vec<T>::load(x + o, xv);
+      Vec16<T>::load(dy + o, gv);
+      if (RELU) Vec16<T>::load(y + o, yv);
+      if (AFF) Vec16<T>::load(x + o, xv);
       if (RELU) {
 #pragma unroll
         for (int j = 0; j < V; ++j)
           if (!(yv[j] > 0.f)) gv[j] = 0.f;
       }
-      if (dres) Vec<T>::store(dres + o, gv);
+      if (dres) Vec16<T>::store(dres + o, gv);
       if (AFF) {
 #pragma unroll
         for (int j = 0; j < V; ++j) {
@@ -193,7 +173,7 @@ __global__ __launch_bounds__(kBlock) void bn_eval_bwd_kernel(const T *__restrict
       if (dx) {
 #pragma unroll
         for (int j = 0; j < V; ++j) gv[j] *= a[j];
-        Vec<T>::store(dx + o, gv);
+        Vec16<T>::store(dx + o, gv);
       }
     }
   }
@@ -236,8 +216,6 @@ __global__ __launch_bounds__(kBlock) void bn_eval_param_grad_kernel(const float 
   if (py == 0 && col < C2) dgb[col] = ((red[0][cx] + red[1][cx]) + red[2][cx]) + red[3][cx];
 }
 
-inline int elem_size(int dtype) { return dtype == 1 ? 2 : 4; }
-
 inline bool shape_ok(long long M, int C, int dtype) {
   if (dtype != 0 && dtype != 1) return false;
   const int V = 16 / elem_size(dtype);
@@ -275,8 +253,6 @@ inline int parts_for(const Shape &sh, int dtype) {
   if (cap > kMaxBlocks) cap = kMaxBlocks;
   return grid_for(sh, cap);
 }
-
-inline bool aligned16(const void *p) { return ((uintptr_t)p % 16) == 0; }
 
 template <typename T>
 void launch_fwd(const void *x, const void *res, const float *gamma, const float *beta, const float *rmean, const float *rvar,

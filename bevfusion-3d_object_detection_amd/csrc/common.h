@@ -8,6 +8,7 @@
 #include <atomic>
 
 #include "../../include/bevfusion_hip.h"
+#include "bf16.h"
 
 #define BFHIP_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -34,6 +35,9 @@ void prof_end(ProfScope *sc);
 inline int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+inline bool aligned16(const void *p) { return ((uintptr_t)p % 16) == 0; }  // true for nullptr: optional tensors pass
+inline int elem_size(int dtype) { return dtype == 1 ? 2 : 4; }             // dtype of the C ABI: 0 = f32, 1 = bf16
 
 // bump allocator over the caller-provided workspace
 struct Workspace {

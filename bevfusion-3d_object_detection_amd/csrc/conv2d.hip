@@ -139,7 +139,7 @@ __device__ __forceinline__ void igemm_epilogue(f32x16 (&acc)[MI][NI], unsigned c
         const int row = wm * (MI * 32) + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
         const float v = acc[mi][ni][r] + bv;
         if (OUT_F32) *(float *)(smem + row * ROWB + col * 4) = v;
-        else *(bf16_t *)(smem + row * ROWB + col * 2) = (bf16_t)rne_bf16(v);
+        else *(bf16_t *)(smem + row * ROWB + col * 2) = (bf16_t)bf16_rne(v);
       }
   }
   __syncthreads();
@@ -177,7 +177,7 @@ __device__ __forceinline__ void igemm_epilogue(f32x16 (&acc)[MI][NI], unsigned c
         for (int q = 0; q < 4; ++q) {
           const float lo = __uint_as_float(a[q] << 16) + __uint_as_float(b[q] << 16);
           const float hi = __uint_as_float(a[q] & 0xffff0000u) + __uint_as_float(b[q] & 0xffff0000u);
-          o[q] = rne_bf16(lo) | (rne_bf16(hi) << 16);
+          o[q] = bf16_rne(lo) | (bf16_rne(hi) << 16);
         }
         *(uint4 *)dst = make_uint4(o[0], o[1], o[2], o[3]);
         continue;
@@ -187,10 +187,10 @@ __device__ __forceinline__ void igemm_epilogue(f32x16 (&acc)[MI][NI], unsigned c
           const unsigned a = *(const unsigned *)(s16 + e), b = *(const unsigned *)(rs + e);
           const float lo = __uint_as_float(a << 16) + __uint_as_float(b << 16);
           const float hi = __uint_as_float(a & 0xffff0000u) + __uint_as_float(b & 0xffff0000u);
-          *(unsigned *)(d16 + e) = rne_bf16(lo) | (rne_bf16(hi) << 16);
+          *(unsigned *)(d16 + e) = bf16_rne(lo) | (bf16_rne(hi) << 16);
         } else {
           for (int q = e; q < e + 2 && col + q < Kout; ++q)
-            d16[q] = (bf16_t)rne_bf16(__uint_as_float((unsigned)s16[q] << 16) + __uint_as_float((unsigned)rs[q] << 16));
+            d16[q] = (bf16_t)bf16_rne(__uint_as_float((unsigned)s16[q] << 16) + __uint_as_float((unsigned)rs[q] << 16));
         }
       }
       continue;
@@ -531,7 +531,7 @@ __global__ __launch_bounds__(256) void conv_weight_transpose_batched_kernel(cons
     bf16_t v = 0;
     if (co < sg.Cout && ci < sg.Cin) {
       const size_t i = ((size_t)co * sg.taps + tap) * sg.Cin + ci;
-      v = sg.src_f32 ? (bf16_t)rne_bf16(((const float *)sg.src)[i]) : ((const bf16_t *)sg.src)[i];
+      v = sg.src_f32 ? (bf16_t)bf16_rne(((const float *)sg.src)[i]) : ((const bf16_t *)sg.src)[i];
     }
     tile[r][tx] = v;
   }
@@ -557,8 +557,8 @@ __global__ __launch_bounds__(256) void split_bf16x3_kernel(const float *__restri
   unsigned hi[8], lo[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
-    hi[j] = rne_bf16(v[j]);
-    lo[j] = rne_bf16(v[j] - __uint_as_float(hi[j] << 16));
+    hi[j] = bf16_rne(v[j]);
+    lo[j] = bf16_rne(v[j] - __uint_as_float(hi[j] << 16));
   }
   const uint4 H4 = make_uint4(hi[0] | (hi[1] << 16), hi[2] | (hi[3] << 16), hi[4] | (hi[5] << 16), hi[6] | (hi[7] << 16));
   const uint4 L4 = make_uint4(lo[0] | (lo[1] << 16), lo[2] | (lo[3] << 16), lo[4] | (lo[5] << 16), lo[6] | (lo[7] << 16));

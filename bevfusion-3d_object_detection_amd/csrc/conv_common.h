@@ -8,7 +8,6 @@
 namespace bfhip {
 namespace {
 
-typedef unsigned short bf16_t;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) short short4_t;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
@@ -43,12 +42,6 @@ struct ConvGeom {
   struct ParityClass { int h0, w0, Hc, Wc, kh0, kw0, nkh, nkw, tile0; } cls[17];
   int ncls;
 };
-
-__device__ __forceinline__ unsigned rne_bf16(float f) {
-  unsigned u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
-  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
 
 __device__ __forceinline__ void glds16(const void *src, void *lds_dst) {
   __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1))) *)src,

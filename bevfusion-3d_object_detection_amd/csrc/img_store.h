@@ -1,20 +1,12 @@
 // img_store.h -- what the kernels that write the image batch share (preprocess.hip, image_aug.hip): the run of kRun pixels a
-// lane owns, its vector / element-wise loads, the fp32 -> bf16 rounding and the 16-byte / element-wise stores of a run.
+// lane owns, its vector / element-wise loads and the 16-byte / element-wise stores of a run.
 #pragma once
 #include "common.h"
 
 namespace bfhip {
 namespace {
 
-typedef unsigned short bf16_t;
-
 constexpr int kRun = 8;  // pixels per lane
-
-__device__ __forceinline__ unsigned bf16_rne(float f) {  // fp32 -> bf16, round to nearest even; NaN -> 0x7fc0 as torch does
-  const unsigned u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7fc0u;
-  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
 
 // kRun source elements as fp32: one aligned vector access, or the first n element by element (the rest are never used)
 __device__ __forceinline__ void load_run(const uint8_t *p, int n, float *o) {
@@ -55,20 +47,21 @@ __device__ __forceinline__ void store_run(float *q, const float *e, bool vec, in
 }
 template <int N>
 __device__ __forceinline__ void store_run(bf16_t *q, const float *e, bool vec, int n) {
+  // NaN-canonical rounding: what torch gives for the same cast; pixels are finite, so the NaN rule never decides a bit here
   if (vec) {
 #pragma unroll
     for (int k = 0; k < N; k += 8) {
       uint4 v;
-      v.x = bf16_rne(e[k]) | (bf16_rne(e[k + 1]) << 16);
-      v.y = bf16_rne(e[k + 2]) | (bf16_rne(e[k + 3]) << 16);
-      v.z = bf16_rne(e[k + 4]) | (bf16_rne(e[k + 5]) << 16);
-      v.w = bf16_rne(e[k + 6]) | (bf16_rne(e[k + 7]) << 16);
+      v.x = bf16_rne_nan_canonical(e[k]) | (bf16_rne_nan_canonical(e[k + 1]) << 16);
+      v.y = bf16_rne_nan_canonical(e[k + 2]) | (bf16_rne_nan_canonical(e[k + 3]) << 16);
+      v.z = bf16_rne_nan_canonical(e[k + 4]) | (bf16_rne_nan_canonical(e[k + 5]) << 16);
+      v.w = bf16_rne_nan_canonical(e[k + 6]) | (bf16_rne_nan_canonical(e[k + 7]) << 16);
       *(uint4 *)(q + k) = v;
     }
   } else {
 #pragma unroll
     for (int k = 0; k < N; ++k)
-      if (k < n) q[k] = (bf16_t)bf16_rne(e[k]);
+      if (k < n) q[k] = (bf16_t)bf16_rne_nan_canonical(e[k]);
   }
 }
 

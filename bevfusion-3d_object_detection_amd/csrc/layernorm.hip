@@ -20,32 +20,19 @@
 namespace bfhip {
 namespace {
 
-typedef unsigned short bf16_t;
-
 constexpr int kNch = 3;            // 8-element chunks a lane can hold
 constexpr int kMaxC = kNch * 8 * kWave;  // 1536
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / kWave;
 constexpr int kMaxBlocks = 1024;   // grid cap (the backward's partial buffer has one row per block)
 
-__device__ __forceinline__ unsigned rne(float f) {  // fp32 -> bf16, round to nearest even (NaN kept quiet)
-  unsigned u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
-  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
-__device__ __forceinline__ float round_bf16(float f) { return __uint_as_float(rne(f) << 16); }
+__device__ __forceinline__ float round_bf16(float f) { return bf16_to_f32(bf16_rne(f)); }
 
 // 8 consecutive elements starting at element e of a bf16 (bf != 0) or f32 array; e is a multiple of 8 and the base 16-byte aligned.
 // The dtype flag is uniform over the launch.
 __device__ __forceinline__ void load8(const void *base, size_t e, int bf, float *o) {
   if (bf) {
-    const uint4 v = *(const uint4 *)((const bf16_t *)base + e);
-    const unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      o[2 * i] = __uint_as_float(w[i] << 16);
-      o[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-    }
+    unpack8(*(const uint4 *)((const bf16_t *)base + e), o);
   } else {
     const float4 *p = (const float4 *)((const float *)base + e);
     const float4 a = p[0], b = p[1];
@@ -56,12 +43,7 @@ __device__ __forceinline__ void load8(const void *base, size_t e, int bf, float 
 
 __device__ __forceinline__ void store8(void *base, size_t e, int bf, const float *o) {
   if (bf) {
-    uint4 v;
-    v.x = rne(o[0]) | (rne(o[1]) << 16);
-    v.y = rne(o[2]) | (rne(o[3]) << 16);
-    v.z = rne(o[4]) | (rne(o[5]) << 16);
-    v.w = rne(o[6]) | (rne(o[7]) << 16);
-    *(uint4 *)((bf16_t *)base + e) = v;
+    *(uint4 *)((bf16_t *)base + e) = pack8(o);
   } else {
     float4 *p = (float4 *)((float *)base + e);
     p[0] = make_float4(o[0], o[1], o[2], o[3]);
@@ -334,8 +316,6 @@ inline int grid_for(long long M, int C) {
   const long long iters = (slabs + kMaxBlocks - 1) / kMaxBlocks;
   return (int)((slabs + iters - 1) / iters);
 }
-
-inline bool aligned16(const void *p) { return ((uintptr_t)p % 16) == 0; }
 
 #define BFHIP_LN_DISPATCH(LPR_VALUE, ...)                      \
   switch (LPR_VALUE) {                                         \

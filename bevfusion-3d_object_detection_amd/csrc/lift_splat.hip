@@ -231,12 +231,6 @@ __global__ __launch_bounds__(256) void plan_group_key_kernel(const unsigned *__r
 // ------------------------------------------------------------------------------ fused forward
 constexpr int kU = 8;
 
-__device__ __forceinline__ unsigned rne_bf16_bits(float f) {  // fp32 -> bf16, round to nearest even (NaN kept quiet)
-  unsigned u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
-  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
-
 // cq lanes per interval, each lane owns 4 channels.  out[cell][c] = sum_i depth[pix_i, d_i] * feat[pix_i, c]
 // OUT16: the fp32 sum is rounded once and stored as bf16 (what the consumer's cast would do: the view transform's bf16
 // downsample convolution then takes the BEV map as it is)
@@ -295,8 +289,8 @@ __global__ __launch_bounds__(256) void lift_splat_fwd_kernel(
   const size_t o = (size_t)cell_of_interval[k] * cq + q;
   if (OUT16) {
     uint2 v;
-    v.x = rne_bf16_bits(acc.x) | (rne_bf16_bits(acc.y) << 16);
-    v.y = rne_bf16_bits(acc.z) | (rne_bf16_bits(acc.w) << 16);
+    v.x = bf16_rne(acc.x) | (bf16_rne(acc.y) << 16);
+    v.y = bf16_rne(acc.z) | (bf16_rne(acc.w) << 16);
     ((uint2 *)out_)[o] = v;
   } else {
     ((float4 *)out_)[o] = acc;
@@ -391,10 +385,10 @@ __device__ __forceinline__ void widen8(const uint4 v, float f[8]) {
 
 __device__ __forceinline__ uint4 narrow8(const float f[8]) {
   uint4 v;
-  v.x = rne_bf16_bits(f[0]) | (rne_bf16_bits(f[1]) << 16);
-  v.y = rne_bf16_bits(f[2]) | (rne_bf16_bits(f[3]) << 16);
-  v.z = rne_bf16_bits(f[4]) | (rne_bf16_bits(f[5]) << 16);
-  v.w = rne_bf16_bits(f[6]) | (rne_bf16_bits(f[7]) << 16);
+  v.x = bf16_rne(f[0]) | (bf16_rne(f[1]) << 16);
+  v.y = bf16_rne(f[2]) | (bf16_rne(f[3]) << 16);
+  v.z = bf16_rne(f[4]) | (bf16_rne(f[5]) << 16);
+  v.w = bf16_rne(f[6]) | (bf16_rne(f[7]) << 16);
   return v;
 }
 

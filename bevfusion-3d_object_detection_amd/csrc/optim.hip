@@ -37,13 +37,6 @@ struct AdamSeg {            // one parameter tensor; all arrays element-for-elem
 
 constexpr int kChunk = 4096, kThreads = 256, kPer = kChunk / kThreads;  // 16 elements per thread
 
-__device__ __forceinline__ float bf16_to_f32(unsigned short h) { return __uint_as_float((unsigned)h << 16); }
-__device__ __forceinline__ unsigned short f32_to_bf16(float f) {
-  unsigned u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40u);
-  return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-
 __device__ __forceinline__ float load_grad(const void *g, int bf16, long long i) {
   return bf16 ? bf16_to_f32(((const unsigned short *)g)[i]) : ((const float *)g)[i];
 }
@@ -132,7 +125,7 @@ __global__ __launch_bounds__(kThreads) void adamw_update_kernel(const AdamSeg *_
     s.master[i] = p;
     s.m[i] = m;
     s.v[i] = v;
-    if (s.lowp) s.lowp[i] = f32_to_bf16(p);
+    if (s.lowp) s.lowp[i] = (bf16_t)bf16_rne(p);
   }
 }
 
@@ -218,7 +211,7 @@ __global__ __launch_bounds__(kThreads) void adamw_update_groups_kernel(const Ada
     s.master[i] = p;
     s.m[i] = m;
     s.v[i] = v;
-    if (s.lowp) s.lowp[i] = f32_to_bf16(p);
+    if (s.lowp) s.lowp[i] = (bf16_t)bf16_rne(p);
   }
 }
 

@@ -15,21 +15,6 @@
 namespace bfhip {
 namespace {
 
-typedef unsigned short bf16_t;
-
-__device__ __forceinline__ void ld8(const bf16_t *p, float *o) {
-  const uint4 v = *(const uint4 *)p;
-  const unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) { o[2 * i] = __uint_as_float(w[i] << 16); o[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u); }
-}
-
-__device__ __forceinline__ unsigned rne(float f) {
-  unsigned u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
-  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
-
 // x [N, H, W, C] -> y [N, OH, OW, C], tap [N, OH, OW, C] (u8); OH = (H - 1) / 2 + 1
 __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const bf16_t *__restrict__ x, int N, int H, int W, int C, int OH, int OW,
                                                           bf16_t *__restrict__ y, unsigned char *__restrict__ tap) {
@@ -105,7 +90,7 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const bf16_t *__restri
       const size_t off = (((size_t)n * OH + oh) * OW + ow) * C + c;
       const uint2 tk = *(const uint2 *)(tap + off);
       float g[8];
-      ld8(dy + off, g);
+      unpack8(*(const uint4 *)(dy + off), g);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const unsigned tj = ((j < 4 ? tk.x : tk.y) >> (8 * (j & 3))) & 0xffu;
@@ -113,10 +98,7 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const bf16_t *__restri
       }
     }
   }
-  uint4 o;
-  o.x = rne(acc[0]) | (rne(acc[1]) << 16); o.y = rne(acc[2]) | (rne(acc[3]) << 16);
-  o.z = rne(acc[4]) | (rne(acc[5]) << 16); o.w = rne(acc[6]) | (rne(acc[7]) << 16);
-  *(uint4 *)(dx + (((size_t)n * H + h) * W + w) * C + c) = o;
+  *(uint4 *)(dx + (((size_t)n * H + h) * W + w) * C + c) = pack8(acc);
 }
 
 }  // namespace

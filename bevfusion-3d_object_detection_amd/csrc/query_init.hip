@@ -274,13 +274,6 @@ __global__ __launch_bounds__(kSelThreads) void qi_select_kernel(Map m, unsigned 
 }
 
 // ---- backward of the row gather: the lowest pick of a cell sums its duplicates in ascending pick order, fp32, one rounding
-__device__ __forceinline__ unsigned short bf16_rne(float f) {
-  unsigned u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7fc0;
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (unsigned short)(u >> 16);
-}
-
 template <bool BF>
 __global__ __launch_bounds__(kSelThreads) void qi_bwd_kernel(const long long *top_index, const void *drows, void *dflat, int K, int Ch,
                                                              long long HW) {
@@ -329,7 +322,8 @@ __global__ __launch_bounds__(kSelThreads) void qi_bwd_kernel(const long long *to
     if (BF) {
       unsigned pk[4];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) pk[e] = (unsigned)bf16_rne(acc[2 * e]) | ((unsigned)bf16_rne(acc[2 * e + 1]) << 16);
+      // every NaN becomes 0x7fc0: the CPU cases compare this gradient against torch's own conversion
+      for (int e = 0; e < 4; ++e) pk[e] = bf16_rne_nan_canonical(acc[2 * e]) | (bf16_rne_nan_canonical(acc[2 * e + 1]) << 16);
       r = make_uint4(pk[0], pk[1], pk[2], pk[3]);
     } else {
       r = make_uint4(__float_as_uint(acc[0]), __float_as_uint(acc[1]), __float_as_uint(acc[2]), __float_as_uint(acc[3]));

@@ -33,11 +33,6 @@ __global__ __launch_bounds__(256) void bev_to_sparse_kernel(const float *__restr
 
 // channels-last variants: out[b][x][y][c*Z + z] (the NHWC memory of the [B, C*Z, X, Y] BEV map), f32 or bf16; a sparse row's
 // C channels land in one (Z-interleaved) segment of the pixel instead of C planes X*Y apart
-__device__ __forceinline__ unsigned short f32_to_bf16_rne(float f) {
-  unsigned u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40u);
-  return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
 
 template <typename T>
 __global__ __launch_bounds__(256) void sparse_to_bev_nhwc_kernel(const float *__restrict__ feats,
@@ -50,7 +45,7 @@ __global__ __launch_bounds__(256) void sparse_to_bev_nhwc_kernel(const float *__
   int4 id = indices[n];
   if (id.x < 0) return;  // inactive row
   size_t o = (((size_t)id.x * X + id.y) * Y + id.z) * ((size_t)C * Z) + (size_t)c * Z + id.w;
-  if (sizeof(T) == 2) ((unsigned short *)out)[o] = f32_to_bf16_rne(feats[t]);
+  if (sizeof(T) == 2) ((bf16_t *)out)[o] = (bf16_t)bf16_rne(feats[t]);
   else ((float *)out)[o] = feats[t];
 }
 

@@ -24,7 +24,6 @@
 namespace bfhip {
 namespace {
 
-typedef unsigned short bf16_t;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -43,13 +42,7 @@ struct Geo {
   float scale;
 };
 
-__device__ __forceinline__ float bf2f(unsigned v) { return __uint_as_float(v << 16); }
-__device__ __forceinline__ unsigned f2bf(float f) {
-  unsigned u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
-  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
-__device__ __forceinline__ unsigned pack2(float lo, float hi) { return f2bf(lo) | (f2bf(hi) << 16); }
+__device__ __forceinline__ unsigned pack2(float lo, float hi) { return bf16_rne(lo) | (bf16_rne(hi) << 16); }
 __device__ __forceinline__ uint4 ld16(const bf16_t *p) { return *(const uint4 *)p; }
 __device__ __forceinline__ uint4 zero16() { return make_uint4(0u, 0u, 0u, 0u); }
 __device__ __forceinline__ unsigned elem(const uint4 &v, int j) {  // bf16 element j of 8 (j a compile-time constant)
@@ -222,7 +215,7 @@ __global__ __launch_bounds__(256) void swin_attn_bwd_kernel(const bf16_t *__rest
       const uint4 of = ok ? ld16(out + orow) : zero16();
       float d = 0.f;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) d += bf2f(elem(gf[mt], j)) * bf2f(elem(of, j));
+      for (int j = 0; j < 8; ++j) d += bf16_to_f32(elem(gf[mt], j)) * bf16_to_f32(elem(of, j));
       d += __shfl_xor(d, 16);
       d += __shfl_xor(d, 32);
       Dq[mt] = d;  // rowsum(dO o O) of token t

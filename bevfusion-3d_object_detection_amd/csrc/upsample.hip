@@ -9,35 +9,6 @@
 namespace bfhip {
 namespace {
 
-typedef unsigned short bf16_t;
-
-template <typename T> struct V;
-template <> struct V<float> {
-  static constexpr int N = 4;
-  static __device__ __forceinline__ void ld(const float *p, float *o) { float4 v = *(const float4 *)p; o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w; }
-  static __device__ __forceinline__ void st(float *p, const float *o) { *(float4 *)p = make_float4(o[0], o[1], o[2], o[3]); }
-};
-template <> struct V<bf16_t> {
-  static constexpr int N = 8;
-  static __device__ __forceinline__ void ld(const bf16_t *p, float *o) {
-    uint4 v = *(const uint4 *)p;
-    const unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { o[2 * i] = __uint_as_float(w[i] << 16); o[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u); }
-  }
-  static __device__ __forceinline__ unsigned r(float f) {
-    unsigned u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
-    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-  }
-  static __device__ __forceinline__ void st(bf16_t *p, const float *o) {
-    uint4 v;
-    v.x = r(o[0]) | (r(o[1]) << 16); v.y = r(o[2]) | (r(o[3]) << 16);
-    v.z = r(o[4]) | (r(o[5]) << 16); v.w = r(o[6]) | (r(o[7]) << 16);
-    *(uint4 *)p = v;
-  }
-};
-
 __device__ __forceinline__ void src_of(int o, int n, int &i0, int &i1, float &w0, float &w1) {
   float s = fmaxf(0.f, ((float)o + 0.5f) * 0.5f - 0.5f);
   i0 = (int)s;
@@ -50,7 +21,7 @@ __device__ __forceinline__ void src_of(int o, int n, int &i0, int &i1, float &w0
 template <typename T>
 __global__ __launch_bounds__(256) void up2x_fwd_kernel(const T *__restrict__ in, int B, int H, int W, int C,
                                                        T *__restrict__ out) {
-  constexpr int N = V<T>::N;
+  constexpr int N = Vec16<T>::V;
   const int cv = C / N;
   long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= (long long)B * 2 * H * 2 * W * cv) return;
@@ -64,22 +35,22 @@ __global__ __launch_bounds__(256) void up2x_fwd_kernel(const T *__restrict__ in,
   src_of(ox, W, x0, x1, wx0, wx1);
   const T *base = in + (size_t)b * H * W * C + c;
   float a[N], q[N], acc[N];
-  V<T>::ld(base + ((size_t)y0 * W + x0) * C, a);
-  V<T>::ld(base + ((size_t)y0 * W + x1) * C, q);
+  Vec16<T>::load(base + ((size_t)y0 * W + x0) * C, a);
+  Vec16<T>::load(base + ((size_t)y0 * W + x1) * C, q);
 #pragma unroll
   for (int j = 0; j < N; ++j) acc[j] = wy0 * (wx0 * a[j] + wx1 * q[j]);
-  V<T>::ld(base + ((size_t)y1 * W + x0) * C, a);
-  V<T>::ld(base + ((size_t)y1 * W + x1) * C, q);
+  Vec16<T>::load(base + ((size_t)y1 * W + x0) * C, a);
+  Vec16<T>::load(base + ((size_t)y1 * W + x1) * C, q);
 #pragma unroll
   for (int j = 0; j < N; ++j) acc[j] += wy1 * (wx0 * a[j] + wx1 * q[j]);
-  V<T>::st(out + (((size_t)b * 2 * H + oy) * 2 * W + ox) * C + c, acc);
+  Vec16<T>::store(out + (((size_t)b * 2 * H + oy) * 2 * W + ox) * C + c, acc);
 }
 
 // gin [B, H, W, C] <- gout [B, 2H, 2W, C]; one thread per (input pixel, channel vector) gathers its <= 5 x 5 candidates
 template <typename T>
 __global__ __launch_bounds__(256) void up2x_bwd_kernel(const T *__restrict__ gout, int B, int H, int W, int C,
                                                        T *__restrict__ gin) {
-  constexpr int N = V<T>::N;
+  constexpr int N = Vec16<T>::V;
   const int cv = C / N;
   long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= (long long)B * H * W * cv) return;
@@ -103,12 +74,12 @@ __global__ __launch_bounds__(256) void up2x_bwd_kernel(const T *__restrict__ gou
       float w = wy * ((x0 == ix ? wx0 : 0.f) + (x1 == ix ? wx1 : 0.f));
       if (w == 0.f) continue;
       float g[N];
-      V<T>::ld(base + ((size_t)oy * 2 * W + ox) * C, g);
+      Vec16<T>::load(base + ((size_t)oy * 2 * W + ox) * C, g);
 #pragma unroll
       for (int j = 0; j < N; ++j) acc[j] += w * g[j];
     }
   }
-  V<T>::st(gin + (((size_t)b * H + iy) * W + ix) * C + c, acc);
+  Vec16<T>::store(gin + (((size_t)b * H + iy) * W + ix) * C + c, acc);
 }
 
 }  // namespace

@@ -144,15 +144,15 @@ __device__ __forceinline__ void wgrad_reduce_body(const float *__restrict__ slab
     }
     if (out_bf16) {
       uint2 o;
-      o.x = rne_bf16(s.x) | (rne_bf16(s.y) << 16);
-      o.y = rne_bf16(s.z) | (rne_bf16(s.w) << 16);
+      o.x = bf16_rne(s.x) | (bf16_rne(s.y) << 16);
+      o.y = bf16_rne(s.z) | (bf16_rne(s.w) << 16);
       *(uint2 *)((bf16_t *)dw + i) = o;
     } else *(float4 *)((float *)dw + i) = s;
   } else {
     for (long long e = i; e < total; ++e) {
       float a = 0.f;
       for (int k = 0; k < splits; ++k) a += slab[(size_t)k * total + e];
-      if (out_bf16) ((bf16_t *)dw)[e] = (bf16_t)rne_bf16(a);
+      if (out_bf16) ((bf16_t *)dw)[e] = (bf16_t)bf16_rne(a);
       else ((float *)dw)[e] = a;
     }
   }
