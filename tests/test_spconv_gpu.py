@@ -631,6 +631,70 @@ def test_gemm_row_tile_variants_vs_fp64(dev, n_rows, kdim, ndim, transpose, flip
     assert 1e-6 < err < 1e-2, err
 
 
+_KV27 = [0.0] + [0.5] * 12 + [1.0] + [0.5] * 12 + [0.05]     # offset 0 empty, 13 (the centre) full, 26 about 5 %, the rest half
+_KV32_ENDS = [1.0] + [0.0] * 30 + [1.0]                      # only the first and the last bit of the 32-bit offset masks
+_KV3 = [1.0, 0.5, 0.05]                                      # the table of ROW_TILE_CASES
+#                    id, n_rows, n_src, densities, kdim, ndim, transpose, flip, use_perm
+EXACT_GEMM_CASES = (
+    # row edges at R = 1: partial tile, partial workgroup, second workgroup; one-ahead (16 -> 16) and two-ahead (64 -> 32) kernel
+    [("rows%d_%dx%d" % (n, k, c), n, 97, _KV27, k, c, 0, 0, False) for n in (1, 17, 70) for k, c in ((16, 16), (64, 32))] +
+    # next-offset shift edge (kk = 31) and the full extent of the two-ahead kernel's staged pair table
+    [("kv32_ends", 70, 97, _KV32_ENDS, 64, 16, 0, 0, False)] +
+    # channel edges: (8, 16) partial 32-chunk one-ahead | (40, 64) NT = 4, partial second chunk | (64, 64) two-ahead NT = 4 |
+    # (72, 24) two-ahead, partial last chunk, column guard inside NT = 2
+    [("ch_%dx%d" % (k, c), 70, 97, _KV27, k, c, 0, 0, False) for k, c in ((16, 16), (8, 16), (40, 64), (64, 64), (72, 24), (128, 128))] +
+    # data gradient of a SubM layer (transposed, flipped offsets) and the mask-sorted form (random row order + row masks)
+    [("dgrad_flip", 70, 97, _KV27, 64, 32, 1, 1, False), ("perm_mask", 70, 97, _KV27, 64, 32, 0, 0, True),
+     ("perm_mask_one_ahead", 70, 97, _KV27, 16, 32, 0, 0, True)] +
+    # row tiles R = 2 and R = 4 (thresholds as in test_gemm_row_tile_variants_vs_fp64), with the NT = 4 instantiations
+    [("tile%d_%dx%d" % (n, k, c), n, 4096, _KV3, k, c, 0, 0, False) for n in (65553, 131089, 262161)
+     for k, c in ((16, 16), (64, 64), (16, 128))])
+
+
+@pytest.mark.parametrize("case", EXACT_GEMM_CASES, ids=lambda c: c[0])
+def test_gemm_exact_integer_parity(dev, case):
+    """Bit-exact gather-GEMM on integer operands, through spconv._gemm: the fp32 entry, the bf16 entry with fp32 storage and the
+    bf16 entry with bf16 storage.  Features are integers in [-3, 3] and weights integers in [-2, 2] (both exact in bf16), so every
+    partial sum is an integer of magnitude <= KV * Kdim * 6 <= 32 * 128 * 6 = 24 576 < 2^24: fp32 accumulation is exact in any
+    order and the fp64 _gemm_reference is THE answer.  An fp32 output must equal it, a bf16 output must equal it rounded once.
+    The tolerance tests above accept 1e-6 < err < 1e-2 on the bf16 paths and cannot see a dropped or doubled term; this can.
+    Pair tables: density per offset as listed in the case; ld = n_rows + 3.  On the fp32 entry the cases with Kdim % 16 != 0,
+    (8, 16), (40, 64) and (72, 24), run the scalar fallback kernel, not an MFMA kernel; they are there for the bf16 entry."""
+    from bevfusion_amd import spconv as sp
+    name, n_rows, n_src, densities, kdim, ndim, transpose, flip, use_perm = case
+    kv = len(densities)
+    assert kv * kdim * 6 < 2 ** 24
+    rs = np.random.RandomState(n_rows % 9973 + kdim * 131 + ndim * 7 + transpose + kv)
+    pairs = np.full((kv, n_rows + 3), -1, np.int32)
+    for k, density in enumerate(densities):
+        m = rs.rand(n_rows) < density
+        pairs[k, :n_rows][m] = rs.randint(0, n_src, int(m.sum()))
+    assert pairs.min() >= -1 and pairs.max() < n_src     # the kernels trust the table
+    cin, cout = (ndim, kdim) if transpose else (kdim, ndim)
+    x = torch.from_numpy(rs.randint(-3, 4, (n_src, kdim)).astype(np.float32))
+    w = torch.from_numpy(rs.randint(-2, 3, (cout, kv, cin)).astype(np.float32))
+    perm = row_mask = None
+    if use_perm:
+        perm = torch.from_numpy(rs.permutation(n_rows).astype(np.int32)).to(dev)
+        bits = (pairs[:, :n_rows] >= 0).astype(np.uint32) << np.arange(kv, dtype=np.uint32)[:, None]
+        row_mask = torch.from_numpy(np.bitwise_or.reduce(bits, axis=0).astype(np.int32)).to(dev)
+    tp, tw = torch.from_numpy(pairs).to(dev), w.to(dev)
+    ref = torch.from_numpy(_gemm_reference(x, w, pairs, n_rows, transpose, flip))
+    assert ref.abs().max() > 0 and torch.equal(ref, ref.round())
+    assert sp._bf16_ok(w, transpose)      # else _gemm would answer the bf16 modes from the fp32 entry, and exactly so
+
+    def run(bf16, io16):
+        tx = x.to(dev).to(torch.bfloat16) if io16 else x.to(dev)
+        out = sp._gemm(tx, tw, tp, n_rows, transpose, flip, perm, row_mask, bf16=bf16, io16=io16)
+        assert out.shape == (n_rows, ndim) and out.dtype == (torch.bfloat16 if io16 else torch.float32)
+        return out.cpu()
+
+    assert torch.equal(run(False, False), ref.float()), "fp32 entry"
+    assert torch.equal(run(True, False), ref.float()), "bf16 entry, fp32 storage"
+    if sp._io16_ok(w, transpose):
+        assert torch.equal(run(True, True), ref.float().to(torch.bfloat16)), "bf16 entry, bf16 storage"
+
+
 def test_sort_rows_is_region_major_mask_sort(dev, sorted_rows):
     """bfhip_rulebook_sort_rows: row_mask bit k = pair present; perm = stable sort by (chunk of 4096 rows, mask)."""
     from bevfusion_amd.spconv import sort_rows
@@ -747,8 +811,9 @@ def test_duplicate_coordinates_semantics_tiny(dev):
 
 
 def test_first_forward_at_the_round2_fault_geometry_is_validated(dev, sorted_rows, monkeypatch):
-    """Round 2 lost a GPU to HSA_STATUS_ERROR_MEMORY_APERTURE_VIOLATION in spconv_gemm_lds_kernel<4,1> (fp32 features, row
-    sorting on, the FIRST forward of a process at batch 4 -- DESIGN.md section 6).  That kernel trusts perm / row_mask / pairs;
+    """Round 2 lost a GPU to HSA_STATUS_ERROR_MEMORY_APERTURE_VIOLATION in spconv_gemm_lds_kernel<4,1>, today's
+    spconv_gemm_kernel<OpF32,4,1> (fp32 features, row sorting on, the FIRST forward of a process at batch 4 -- DESIGN.md
+    section 6).  That kernel trusts perm / row_mask / pairs;
     this runs the same geometry (fresh model, no hints, fp32, no autocast, 4 x 40 k points, forward + backward) with
     bfhip_rulebook_validate in front of every one of the 41 gather launches, and checks that the sorted row order changes no
     bit of the forward."""

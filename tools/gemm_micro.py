@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """Forward gather-GEMM time per distinct sparse layer of the encoder (real rulebooks of the synthetic batch of 4), fp32 and
-bf16 feature storage: the library's profiler scope around the main kernel.  BFHIP_GEMM_V selects the kernel variant while
-two are kept for A/B."""
+bf16 feature storage: the library's profiler scope around the main kernel."""
 import os
 import sys
 
