@@ -170,6 +170,13 @@ SIGNATURES = {
     "bfhip_jpeg_parse": (_c_int, [_c_vp, _c_sz, _c_vp]),
     "bfhip_jpeg_entropy_decode": (_c_int, [_c_vp, _c_sz, _c_vp, _c_vp, _c_sz]),
     "bfhip_jpeg_decode": (_c_int, [_c_vp, _c_vp, _c_int, _c_vp, _c_sz, _c_vp, _c_sz, _c_vp, _c_sz, _c_vp]),
+    "bfhip_jpeg_entropy_encode": (_c_int, [_c_vp, _c_vp, _c_sz, _c_int, _c_vp, _c_sz, _c_vp]),
+    "bfhip_jpeg_encode_supported": (_c_int, [_c_int] * 4),
+    "bfhip_jpeg_encode_workspace_bytes": (_c_sz, [_c_int] * 4),
+    "bfhip_jpeg_encode_max_frames": (_c_int, []),
+    "bfhip_jpeg_forward": (_c_int, [_c_vp, _c_vp, _c_int, _c_vp, _c_sz, _c_vp, _c_sz, _c_vp]),
+    "bfhip_jpeg_entropy_encode_device": (_c_int, [_c_vp, _c_vp, _c_int, _c_vp, _c_sz, _c_vp, _c_sz, _c_vp, _c_sz, _c_vp, _c_vp]),
+    "bfhip_jpeg_encode": (_c_int, [_c_vp, _c_vp, _c_int, _c_vp, _c_sz, _c_vp, _c_sz, _c_vp, _c_sz, _c_vp, _c_sz, _c_vp, _c_vp]),
     "bfhip_points_in_boxes_block": (_c_int, []),
     "bfhip_points_in_boxes_max_boxes": (_c_int, []),
     "bfhip_points_in_boxes_workspace_bytes": (_c_sz, [ctypes.c_longlong, _c_int]),

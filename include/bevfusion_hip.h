@@ -976,6 +976,80 @@ int bfhip_jpeg_decode(const bfhip_jpeg_frame *frames_host, const bfhip_jpeg_fram
                       size_t rgb_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Baseline JPEG encode (csrc/jpeg_encode_host.h, csrc/jpeg_encode.hip): the decoder turned round.  RGB -> YCbCr, edge padding,
+ *   chroma downsampling, libjpeg's accurate integer forward DCT (jfdctint) and quantisation leave int16 coefficients in the
+ *   decoder's layout (per component [block_rows, block_cols, 64], natural order, DC not differenced); the Huffman stage codes
+ *   them with the Annex K tables.  bevfusion_amd/jpeg_encode.py: torch_jpeg_forward defines the coefficients in int32
+ *   wrap-around arithmetic, and the host entropy encoder defines the bytes.  Luma sampling hs x vs is 1x1, 2x1 or 2x2.
+ *   bfhip_jpeg_entropy_encode: HOST ONLY, no HIP call.  header: geometry as bfhip_jpeg_parse leaves it (width, height, hs, vs,
+ *     mcus, block_cols / block_rows, coef_offset, coef_bytes; the quantisation tables are not read); coef_bytes >=
+ *     header->coef_bytes.  restart_interval: MCUs between restart markers, 0 = none, at most 65535.  Writes the scan --
+ *     interleaved MCUs, DC differences per component reset at every restart, zigzag order, ZRL for runs above 15, EOB unless
+ *     coefficient 63 is non-zero, FF stuffed with 00, the last byte of every interval padded with 1-bits, RSTm with m counting
+ *     modulo 8 -- and the EOI marker behind it into out[0 .. capacity).  BFHIP_E_INVALID, with not one byte written at or past
+ *     `capacity`, when the stream is longer than capacity (stats->bytes then holds the needed length), when an AC coefficient
+ *     lies outside +-1023 or a DC difference outside +-2047 (neither has a Huffman code) or when the header is inconsistent.
+ *     stats (may be NULL): bytes written (the needed length on overflow), stuffed bytes, ZRL symbols, EOBs and the largest AC
+ *     and DC categories met.
+ *   The device entry points take a descriptor table, one bfhip_jpeg_enc_frame per frame, in host and in device memory (the same
+ *     bytes; frames_dev 16-byte aligned); the host copy is validated before anything is launched: dimensions 1 .. 65535, a
+ *     sampling bfhip_jpeg_encode_supported takes, block counts that fit the frame, no zero quantisation entry, every range
+ *     inside its buffer, frames in ascending order of out_off and ws_off without overlap, n_frames 1 ..
+ *     bfhip_jpeg_encode_max_frames() = 65535.  Frames of different sizes, samplings and tables share the launches.
+ *     rgb_off: bytes from rgb_dev of the frame's uint8 [height, width, 3] pixels.  coef_off: int16 elements from coef_dev (a
+ *     multiple of 8; coef_dev 16-byte aligned).  out_off / capacity: bytes from out_dev of the frame's stream and how many it
+ *     may take.  ws_off: bytes from the workspace (a multiple of 256) of the frame's bfhip_jpeg_encode_workspace_bytes(width,
+ *     height, hs, vs) bytes.  quant: natural order, components 1 and 2 usually equal.
+ *   bfhip_jpeg_forward (one launch): pixels -> coefficients: jccolor's 16-bit fixed-point colour conversion; components
+ *     extended by repeating their last column and row, the downsampled chroma plane extended by its last downsampled row; h2v2
+ *     (a + b + c + d + bias) >> 2 with bias 1, 2, 1, 2 ..., h2v1 (a + b + bias) >> 1 with bias 0, 1, 0, 1 ...; - 128; rows
+ *     first (outputs 0 and 4 shifted left by 2, the rest descaled by 11), columns second (0 and 4 descaled by 2, the rest by
+ *     15); (|x| + (8 q >> 1)) / (8 q) truncated, sign restored.  A luma block wholly outside ceil(W / 8) x ceil(H / 8) is zero
+ *     but for its DC, which is the DC of the block to its left, or -- in a block row below the last real one -- of the rightmost
+ *     block of the row above within the same MCU (libjpeg's dummy blocks).
+ *   bfhip_jpeg_entropy_encode_device (two launches): coefficients -> each frame's scan with a restart marker after EVERY MCU
+ *     row (the unit of parallelism) and EOI, the bytes the host encoder gives with restart_interval = mcus_x.  result: int64
+ *     [n_frames, 2]: the stream's length -- the NEEDED length when it exceeds the capacity -- and flags: BFHIP_JPEG_ENC_OVERFLOW
+ *     (nothing was written at or past out_off + capacity), BFHIP_JPEG_ENC_BAD_COEF (a coefficient without a Huffman code was met
+ *     and clamped: the stream is not to be used).
+ *   bfhip_jpeg_encode: both (three launches).  The markers in front of the scan are the caller's (jpeg_encode.py).
+ *   Integer arithmetic only (the slab's boundary words are completed with integer atomic OR, which commutes): the same bytes on
+ *   every run.  No allocation, no synchronisation; everything runs on `stream`.
+ * --------------------------------------------------------------------------------------- */
+#define BFHIP_JPEG_ENC_OVERFLOW 1
+#define BFHIP_JPEG_ENC_BAD_COEF 2
+typedef struct bfhip_jpeg_enc_stats {
+  int64_t bytes;
+  int64_t stuffed;
+  int64_t zrl;
+  int64_t eob;
+  int32_t max_ac_category, max_dc_category;
+} bfhip_jpeg_enc_stats;
+typedef struct bfhip_jpeg_enc_frame {
+  int64_t rgb_off;
+  int64_t coef_off[3];
+  int64_t out_off, capacity;
+  int64_t ws_off;
+  int32_t width, height;
+  int32_t hs, vs;
+  int32_t block_cols[3], block_rows[3];
+  uint16_t quant[3][64];
+} bfhip_jpeg_enc_frame;
+int bfhip_jpeg_entropy_encode(const bfhip_jpeg_header *header, const int16_t *coef, size_t coef_bytes, int restart_interval,
+                              uint8_t *out, size_t capacity, bfhip_jpeg_enc_stats *stats);
+int bfhip_jpeg_encode_supported(int width, int height, int hs, int vs);
+size_t bfhip_jpeg_encode_workspace_bytes(int width, int height, int hs, int vs);
+int bfhip_jpeg_encode_max_frames(void);
+int bfhip_jpeg_forward(const bfhip_jpeg_enc_frame *frames_host, const bfhip_jpeg_enc_frame *frames_dev, int n_frames,
+                       const uint8_t *rgb_dev, size_t rgb_bytes, int16_t *coef_dev, size_t coef_elems, void *stream);
+int bfhip_jpeg_entropy_encode_device(const bfhip_jpeg_enc_frame *frames_host, const bfhip_jpeg_enc_frame *frames_dev, int n_frames,
+                                     const int16_t *coef_dev, size_t coef_elems, void *workspace, size_t workspace_bytes,
+                                     uint8_t *out_dev, size_t out_bytes, int64_t *result_dev, void *stream);
+int bfhip_jpeg_encode(const bfhip_jpeg_enc_frame *frames_host, const bfhip_jpeg_enc_frame *frames_dev, int n_frames,
+                      const uint8_t *rgb_dev, size_t rgb_bytes, int16_t *coef_dev, size_t coef_elems, void *workspace,
+                      size_t workspace_bytes, uint8_t *out_dev, size_t out_bytes, int64_t *result_dev, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Points in rotated boxes, per box (csrc/points_in_boxes.hip): box_np_ops.points_in_rbbox (M3D/structures/ops/box_np_ops.py
  *   :354-377, 643-677) and the per-box gathers of the ground-truth database builder (tools/dataset_converters/
  *   create_gt_database.py:257, 296-297), as bevfusion_amd/box_ops.py: torch_points_in_boxes defines them.

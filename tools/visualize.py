@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""Draws saved predictions: per sample a camera mosaic and a bird's-eye plot, written as PNG frames (no mp4: there is no video encoder here).
+"""Draws saved predictions: per sample a camera mosaic and a bird's-eye plot, written as PNG frames and, with --video, as a Motion-JPEG AVI.
 
     visualize.py RESULTS.pkl ANN_FILE --out DIR [--data-root ROOT] [--classes car,truck,...] [--threshold 0.01] [--gt]
                  [--only-classes car truck] [--cam-order 0 1 2] [--scale 3] [--max-vis 10] [--no-track] [--device cuda:0|cpu]
+                 [--video OUT.avi] [--fps 2] [--quality 90] [--video-stream cameras|bev] [--no-png]
     visualize.py --synthetic --out DIR [--frames 3] [--scale 3] [--small]
 
 RESULTS.pkl: the list tools/evaluate.py takes, one entry per sample with 'sample_idx' and 'pred_instances_3d' {'bboxes_3d',
@@ -10,8 +11,10 @@ RESULTS.pkl: the list tools/evaluate.py takes, one entry per sample with 'sample
 `sample_idx` names the camera files (`images`: img_path, lidar2cam, cam2img) and the sweep (`lidar_points`: lidar_path,
 num_pts_feats), relative to --data-root.  --gt draws the infos' `instances` instead of the predictions (no tracking), as the
 reference tool does without --show-pred.  Predictions pass a score threshold, the class filter and the light tracker
-(bevfusion_amd.visualize.Tracker3D).  Out: DIR/cameras/000000.png ... and DIR/bev/000000.png ..., written with Pillow.  The
-reference tools encode an mp4 with OpenCV; video encoding is out of scope here -- feed the PNG frames to any encoder.
+(bevfusion_amd.visualize.Tracker3D).  Out: DIR/cameras/000000.png ... and DIR/bev/000000.png ..., written with Pillow
+(--no-png: not written).  --video OUT.avi also writes the camera mosaics (--video-stream bev: the BEV plots) as a video, as the
+reference tools do -- they encode mp4v into an mp4 with OpenCV; here every frame is a baseline JPEG, encoded on the device from
+the tensor the renderer left there (bevfusion_amd.jpeg_encode.encode_frames), in an AVI file (MjpegAviWriter).
 --synthetic draws seeded frames, sweeps and boxes of the nominal six-camera rig instead (--small: 90 x 160 frames)."""
 import argparse
 import json
@@ -25,6 +28,7 @@ import numpy as np
 import torch
 
 import bevfusion_amd  # noqa: F401
+from bevfusion_amd import jpeg_encode
 from bevfusion_amd import synthetic
 from bevfusion_amd import visualize as vz
 
@@ -86,7 +90,13 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("results", nargs="?")
     ap.add_argument("ann_file", nargs="?")
-    ap.add_argument("--out", required=True, help="output directory of the PNG frames (writing an mp4 is out of scope: no encoder)")
+    ap.add_argument("--out", required=True, help="output directory of the PNG frames")
+    ap.add_argument("--video", default=None, metavar="PATH.avi",
+                    help="also write the frames as a Motion-JPEG AVI (the reference tools write mp4v into an mp4)")
+    ap.add_argument("--fps", type=float, default=2.0, help="frame rate of the video (the reference's: 2)")
+    ap.add_argument("--quality", type=int, default=90, help="JPEG quality of the video's frames")
+    ap.add_argument("--video-stream", choices=("cameras", "bev"), default="cameras")
+    ap.add_argument("--no-png", action="store_true", help="with --video: write no PNG frames")
     ap.add_argument("--synthetic", action="store_true")
     ap.add_argument("--small", action="store_true")
     ap.add_argument("--frames", type=int, default=3)
@@ -103,12 +113,15 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if not args.synthetic and not (args.results and args.ann_file):
         ap.error("RESULTS.pkl and ANN_FILE, or --synthetic")
-    from PIL import Image
+    if args.no_png and not args.video:
+        ap.error("--no-png needs --video")
+    if not args.no_png:
+        from PIL import Image
     classes = args.classes.split(",") if args.classes else NUSC_CLASSES
     dev = torch.device(args.device)
     tracker = None if (args.no_track or args.gt) else vz.Tracker3D(max_missed=3, max_dist=4.0)
     samples = synthetic_samples(args.frames, args.small) if args.synthetic else real_samples(args)
-    written = 0
+    written, writer = 0, None
     for i, (meta, frames, points, what) in enumerate(samples):
         if 0 <= args.max_vis <= i:
             break
@@ -116,11 +129,20 @@ def main(argv=None):
         points_t = None if points is None else torch.from_numpy(np.ascontiguousarray(points, dtype=np.float32)).to(dev)
         mosaic, bev = vz.visualize_sample(meta, frames_t, points_t, what, classes, score_thr=args.threshold,
                                           only_classes=args.only_classes, tracker=tracker, cam_order=args.cam_order, scale=args.scale)
+        shown = mosaic if args.video_stream == "cameras" else bev
+        if args.video and shown is not None:
+            data = jpeg_encode.encode_frames([shown], quality=args.quality)[0]  # from the device tensor on a GPU
+            if writer is None:
+                writer = jpeg_encode.MjpegAviWriter(args.video, args.fps, shown.shape[1], shown.shape[0])
+            writer.write(data)
         for sub, img in (("cameras", mosaic), ("bev", bev)):
-            if img is not None:
+            if img is not None and not args.no_png:
                 os.makedirs(os.path.join(args.out, sub), exist_ok=True)
                 Image.fromarray(img.cpu().numpy()).save(os.path.join(args.out, sub, "%06d.png" % i))
         written += 1
+    if writer is not None:
+        writer.close()
+        print("%d frames in %s (%s path)" % (len(writer.index), args.video, "kernel" if jpeg_encode.PATHS["kernel"] else "host"))
     print("%d samples written under %s (%s path)" % (written, args.out, "kernel" if vz.PATHS["kernel"] else "host"))
     return 0
 
