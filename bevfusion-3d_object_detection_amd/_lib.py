@@ -95,6 +95,7 @@ SIGNATURES = {
     "bfhip_rotate_nms_workspace_bytes": (_c_sz, [_c_int, _c_int]),
     "bfhip_rotate_nms": (_c_int, [_c_vp, _c_vp, _c_int, ctypes.c_float, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_sz, _c_vp]),
     "bfhip_decode_boxes": (_c_int, [_c_vp] * 5 + [_c_int] * 4 + [_c_vp, _c_vp, _c_vp]),
+    "bfhip_predict_compact": (_c_int, [_c_vp] * 3 + [_c_int] * 3 + [_c_vp, _c_int, ctypes.c_float] + [_c_vp] * 5),
     "bfhip_assign_cost": (_c_int, [_c_vp, _c_int, _c_vp, _c_int, _c_int, _c_int, _c_vp, _c_int, _c_vp, _c_vp] + [_c_int] * 3 +
                           [_c_vp] * 4),
     "bfhip_hungarian": (_c_int, [_c_vp, _c_vp, _c_int, _c_int, _c_int, _c_vp, _c_vp, _c_vp]),
@@ -145,6 +146,9 @@ SIGNATURES = {
     "bfhip_bn_eval_parts": (_c_int, [ctypes.c_longlong, _c_int, _c_int]),
     "bfhip_bn_eval_fwd": (_c_int, [_c_vp] * 6 + [ctypes.c_longlong, _c_int, _c_int, ctypes.c_float, _c_int, _c_vp, _c_vp]),
     "bfhip_bn_eval_bwd": (_c_int, [_c_vp] * 6 + [ctypes.c_longlong, _c_int, _c_int, ctypes.c_float, _c_int] + [_c_vp] * 5),
+    "bfhip_bn_eval_rows_fwd": (_c_int, [_c_vp] * 6 + [ctypes.c_longlong, _c_int, _c_int, ctypes.c_float, _c_int, _c_vp, _c_vp,
+                                         _c_vp]),
+    "bfhip_bn_eval_rows_bwd": (_c_int, [_c_vp] * 6 + [ctypes.c_longlong, _c_int, _c_int, ctypes.c_float, _c_int] + [_c_vp] * 6),
     "bfhip_img_preprocess_max_samples": (_c_int, []),
     "bfhip_img_preprocess": (_c_int, [_c_vp] + [_c_int] * 5 + [_c_vp, _c_vp, ctypes.c_float, _c_int, _c_int, _c_int, _c_int,
                                       _c_vp, _c_vp]),

@@ -70,7 +70,10 @@ class BEVFusion(nn.Module):
         # count on the device, ZERO host reads per forward; the first forward runs the exact path to learn them.
         # Opt-in (BFHIP_STATIC_LIDAR=1, or a captured hipGraph, which needs it): on the side stream the two host reads of the
         # exact path cost nothing measurable, while capacity-sized buffers add 0.6 ms (slack 1.05) to 1.3 ms (slack 1.5) of
-        # GPU work per batch-4 step (36.9 exact vs 37.5 / 37.7 / 38.2 ms, same box, bench.py `full`)
+        # GPU work per batch-4 step (36.9 exact vs 37.5 / 37.7 / 38.2 ms, same box, bench.py `full`).
+        # Training and eval share the switch and the (grow-only) capacities; in eval the sparse BatchNorms mask the rows beyond
+        # the count themselves (bfhip_bn_eval_rows_fwd), there is no loss to poison on overflow, and predict(packed=True)
+        # returns the overflow flag with its result -- a predict() that reads nothing back ("Sync-free predict")
         self.static_lidar = os.environ.get("BFHIP_STATIC_LIDAR", "0") == "1"
         self._voxel_cap = None
         self._voxel_monitor = None
@@ -162,7 +165,7 @@ class BEVFusion(nn.Module):
     def _static_lidar_ready(self):
         layer, enc = self.pts_voxel_layer, self.pts_middle_encoder
         hard = layer.max_num_points != -1 and (layer.max_voxels[0] if self.training else layer.max_voxels[1]) != -1
-        return (self.static_lidar and hard and self.voxelize_reduce and self.training and self._voxel_cap is not None
+        return (self.static_lidar and hard and self.voxelize_reduce and self._voxel_cap is not None
                 and getattr(enc, "static_caps", None) is not None)
 
     def extract_pts_feat(self, batch_inputs_dict) -> torch.Tensor:
@@ -324,11 +327,17 @@ class BEVFusion(nn.Module):
             f.record_stream(main)  # produced on the LiDAR side stream, consumed behind main.wait_stream(side)
         return flags[0] if len(flags) == 1 else flags[0] | flags[1]
 
-    def predict(self, batch_inputs_dict, batch_data_samples=None, **kwargs):
-        """BF/bevfusion.py:257-303 without the Det3DDataSample packaging: one dict of boxes/scores/labels per sample."""
+    def predict(self, batch_inputs_dict, batch_data_samples=None, packed=False, **kwargs):
+        """BF/bevfusion.py:257-303 without the Det3DDataSample packaging: one dict of boxes/scores/labels per sample.
+        packed=True: a head_targets.PackedPredictions instead (padded rows, counts and the static capacity mode's overflow flag
+        on the device), built without a host read; its to_list() gives the list."""
         metas = [getattr(d, "metainfo", None) for d in (batch_data_samples or [])] or None
         feats, _ = self.extract_feat(batch_inputs_dict, metas)
-        return self.bbox_head.predict(feats, metas)
+        if not packed:
+            return self.bbox_head.predict(feats, metas)
+        out = self.bbox_head.predict(feats, metas, packed=True)
+        out.overflow = self.capacity_status()
+        return out
 
     # ------------------------------------------------------------------ mmengine's BaseModel entry points
     def preprocess(self, data, training=False):

@@ -171,14 +171,21 @@ def _dense_as(t, dtype, dim):
     return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.preserve_format)
 
 
-def _eval_fwd(x, residual, weight, bias, running_mean, running_var, eps, relu):
+def _eval_fwd(x, residual, weight, bias, running_mean, running_var, eps, relu, rows_dev=None):
+    """rows_dev (optional int32[1] device tensor): x is capacity-sized, only its first *rows_dev rows are active and the rest of y
+    is written as zeros (bfhip_bn_eval_rows_fwd)."""
     C = x.shape[1]
     res = _dense_as(residual, x.dtype, x.dim()) if residual is not None else None
     y = torch.empty_like(x)  # keeps the strides
     with torch.cuda.device(x.device):
-        _lib.call("bfhip_bn_eval_fwd", x.data_ptr(), _lib.ptr(res), weight.data_ptr(), bias.data_ptr(), running_mean.data_ptr(),
-                  running_var.data_ptr(), x.numel() // C, C, _DT[x.dtype], float(eps), 1 if relu else 0, y.data_ptr(),
-                  _lib.stream_of(x))
+        if rows_dev is None:
+            _lib.call("bfhip_bn_eval_fwd", x.data_ptr(), _lib.ptr(res), weight.data_ptr(), bias.data_ptr(),
+                      running_mean.data_ptr(), running_var.data_ptr(), x.numel() // C, C, _DT[x.dtype], float(eps),
+                      1 if relu else 0, y.data_ptr(), _lib.stream_of(x))
+        else:
+            _lib.call("bfhip_bn_eval_rows_fwd", x.data_ptr(), _lib.ptr(res), weight.data_ptr(), bias.data_ptr(),
+                      running_mean.data_ptr(), running_var.data_ptr(), x.numel() // C, C, _DT[x.dtype], float(eps),
+                      1 if relu else 0, y.data_ptr(), rows_dev.data_ptr(), _lib.stream_of(x))
     EVAL_LAUNCHES["fwd"] += 1
     return y
 
@@ -187,8 +194,9 @@ class _BNEvalFunction(torch.autograd.Function):
     """y = act(BN_eval(x) [+ residual]); x, residual, y dense [M, C] in memory, f32 or bf16."""
 
     @staticmethod
-    def forward(ctx, x, residual, weight, bias, running_mean, running_var, eps, relu):
-        y = _eval_fwd(x, residual, weight, bias, running_mean, running_var, eps, relu)
+    def forward(ctx, x, residual, weight, bias, running_mean, running_var, eps, relu, rows_dev=None):
+        y = _eval_fwd(x, residual, weight, bias, running_mean, running_var, eps, relu, rows_dev)
+        ctx.rows_dev = rows_dev
         need = ctx.needs_input_grad
         ctx.affine = need[2] or need[3]
         ctx.save_for_backward(x if ctx.affine else None, y if relu else None, weight, running_mean, running_var)
@@ -203,15 +211,17 @@ class _BNEvalFunction(torch.autograd.Function):
         need = ctx.needs_input_grad
         want_dx, want_dres, affine = need[0], need[1], ctx.affine
         if not (want_dx or want_dres or affine):
-            return (None,) * 8
+            return (None,) * 9
         dy = _dense_as(dy, ctx.x_dtype, ctx.x_dim)
         C = dy.shape[1]
         M, dt = dy.numel() // C, _DT[dy.dtype]
         dx = torch.empty_like(dy) if want_dx else None
+        rows_dev = ctx.rows_dev
         dres = None
         if want_dres:
-            dres = torch.empty_like(dy) if ctx.relu else dy  # without ReLU the residual's gradient IS dy
-        kernel_dres = dres if ctx.relu else None
+            # without ReLU the residual's gradient IS dy -- except beyond a device-side row count, where it is zero
+            dres = torch.empty_like(dy) if ctx.relu or rows_dev is not None else dy
+        kernel_dres = dres if ctx.relu or rows_dev is not None else None
         partial = dgb = None
         if affine:
             parts = _lib.load().bfhip_bn_eval_parts(M, C, dt)
@@ -219,20 +229,25 @@ class _BNEvalFunction(torch.autograd.Function):
             dgb = torch.empty(2 * C, dtype=torch.float32, device=dy.device)
         if dx is not None or kernel_dres is not None or affine:
             with torch.cuda.device(dy.device):
-                _lib.call("bfhip_bn_eval_bwd", dy.data_ptr(), _lib.ptr(y), _lib.ptr(x) if affine else None, weight.data_ptr(),
-                          running_mean.data_ptr(), running_var.data_ptr(), M, C, dt, ctx.eps, 1 if ctx.relu else 0, _lib.ptr(dx),
-                          _lib.ptr(kernel_dres), _lib.ptr(partial), _lib.ptr(dgb), _lib.stream_of(dy))
+                head = (dy.data_ptr(), _lib.ptr(y), _lib.ptr(x) if affine else None, weight.data_ptr(), running_mean.data_ptr(),
+                        running_var.data_ptr(), M, C, dt, ctx.eps, 1 if ctx.relu else 0, _lib.ptr(dx), _lib.ptr(kernel_dres),
+                        _lib.ptr(partial), _lib.ptr(dgb))
+                if rows_dev is None:
+                    _lib.call("bfhip_bn_eval_bwd", *head, _lib.stream_of(dy))
+                else:
+                    _lib.call("bfhip_bn_eval_rows_bwd", *head, rows_dev.data_ptr(), _lib.stream_of(dy))
             EVAL_LAUNCHES["bwd"] += 1
         if dres is not None and ctx.res_dtype != dres.dtype:
             dres = dres.to(ctx.res_dtype)
         dw = dgb[:C].to(weight.dtype) if need[2] else None
         db = dgb[C:].to(weight.dtype) if need[3] else None
-        return dx, dres, dw, db, None, None, None, None
+        return dx, dres, dw, db, None, None, None, None, None
 
 
-def eval_apply(mod, x, residual, relu):
-    """The eval-mode forward of BatchNorm module `mod` on the kernels (the caller has checked `_eval_fusable(mod, x)`)."""
-    args = (x, residual, mod.weight, mod.bias, mod.running_mean, mod.running_var, mod.eps, bool(relu))
+def eval_apply(mod, x, residual, relu, rows_dev=None):
+    """The eval-mode forward of BatchNorm module `mod` on the kernels (the caller has checked `_eval_fusable(mod, x)`).
+    rows_dev (int32[1] device tensor): x is a capacity-sized [M, C] matrix with *rows_dev active rows; the others come out zero."""
+    args = (x, residual, mod.weight, mod.bias, mod.running_mean, mod.running_var, mod.eps, bool(relu), rows_dev)
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in args[:4]):
         return _BNEvalFunction.apply(*args)
     return _eval_fwd(*args)

@@ -14,6 +14,12 @@
 // and a workgroup covers R = 256 / L consecutive rows per iteration: one iteration reads R * L * 16 contiguous bytes.  A row
 // of more than 256 vectors (up to 512: 2048 f32 channels) is cut into column tiles of 256 (blockIdx.y), R = 1.  The grid is
 // capped at 2048 workgroups, which stride over the row groups.
+//
+// ROWS variants (bfhip_bn_eval_rows_*): the matrix is capacity-sized and only its first n = clamp(*rows_dev, 0, M) rows are
+// active, n living on the device (static capacity mode of the sparse encoder).  Every workgroup reads n itself (one uniform
+// load), walks the same row groups as the plain kernel over the capacity, and writes zeros to the rows [n, M) whatever the
+// inputs hold there: their loads are still issued (in bounds) so the load pipeline is the plain kernel's, and their values are
+// dropped by selects, never multiplied.  An active row gets the plain kernel's arithmetic, so its bits are the same.
 #include "common.h"
 
 namespace bfhip {
@@ -82,14 +88,23 @@ __device__ __forceinline__ void walk_groups(const Shape &sh, const Lane &ln, Loa
   }
 }
 
-template <typename T, bool RES, bool RELU>
+// first element offset beyond the active rows: offset o = row * C + col (col < C) is in an active row iff o < end
+__device__ __forceinline__ size_t active_end(const int *rows_dev, const Shape &sh) {
+  long long n = *rows_dev;  // uniform address: one scalar load per workgroup
+  n = n < 0 ? 0 : (n > sh.M ? sh.M : n);
+  return (size_t)n * sh.C;
+}
+
+template <typename T, bool RES, bool RELU, bool ROWS>
 __global__ __launch_bounds__(kBlock) void bn_eval_fwd_kernel(const T *__restrict__ x, const T *__restrict__ res,
                                                              const float *__restrict__ gamma, const float *__restrict__ beta,
                                                              const float *__restrict__ rmean, const float *__restrict__ rvar,
-                                                             float eps, Shape sh, T *__restrict__ y) {
+                                                             float eps, Shape sh, T *__restrict__ y,
+                                                             const int *__restrict__ rows_dev) {
   constexpr int V = Vec16<T>::V;
   const Lane ln = lane_of<V>(sh);
   if (!ln.live) return;
+  const size_t end = ROWS ? active_end(rows_dev, sh) : 0;
   float a[V], mean[V], b[V];
   {
     float var[V];
@@ -113,6 +128,7 @@ __global__ __launch_bounds__(kBlock) void bn_eval_fwd_kernel(const T *__restrict
           float r = fmaf(w.v[j] - mean[j], a[j], b[j]);
           if (RES) r += w.q[j];
           w.v[j] = (RELU && !(r > 0.f)) ? 0.f : r;
+          if (ROWS && o >= end) w.v[j] = 0.f;
         }
         if (keep) Vec16<T>::store(y + o, w.v);
       });
@@ -120,12 +136,13 @@ __global__ __launch_bounds__(kBlock) void bn_eval_fwd_kernel(const T *__restrict
 
 // dx and dres are written where their pointer is given (uniform over the launch).  AFF: also accumulate this workgroup's
 // partial row [2][C] = (sum g * x_hat, sum g) over its rows.
-template <typename T, bool RELU, bool AFF>
+template <typename T, bool RELU, bool AFF, bool ROWS>
 __global__ __launch_bounds__(kBlock) void bn_eval_bwd_kernel(const T *__restrict__ dy, const T *__restrict__ y,
                                                              const T *__restrict__ x, const float *__restrict__ gamma,
                                                              const float *__restrict__ rmean, const float *__restrict__ rvar,
                                                              float eps, Shape sh, T *__restrict__ dx, T *__restrict__ dres,
-                                                             float *__restrict__ partial) {
+                                                             float *__restrict__ partial,
+                                                             const int *__restrict__ rows_dev) {
   constexpr int V = Vec16<T>::V;
   __shared__ float sm[AFF ? 2 * kBlock * V : 1];
   const int t = threadIdx.x;
@@ -148,7 +165,7 @@ __global__ __launch_bounds__(kBlock) void bn_eval_bwd_kernel(const T *__restrict
       for (int j = 0; j < V; ++j) a[j] *= rstd[j];
     }
     if (AFF) load_param<V>(rmean, ln.cv * V, mean);
-    const size_t col = (size_t)ln.cv * V;
+    const size_t end = ROWS ? active_end(rows_dev, sh) : 0;
     for (long long g = blockIdx.x; g < sh.groups; g += gridDim.x) {
       const long long r = g * sh.R + ln.rl;
       if (r >= sh.M) break;  // only the last group can be short
@@ -161,6 +178,13 @@ __global__ __launch_bounds__(kBlock) void bn_eval_bwd_kernel(const T *__restrict
 #pragma unroll
         for (int j = 0; j < V; ++j)
           if (!(yv[j] > 0.f)) gv[j] = 0.f;
+      }
+      if (ROWS && o >= end) {  // a row beyond the count: g = 0 and x_hat = 0, so dx = dres = 0 and the sums get exact zeros
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+          gv[j] = 0.f;
+          if (AFF) xv[j] = mean[j];
+        }
       }
       if (dres) Vec16<T>::store(dres + o, gv);
       if (AFF) {
@@ -256,26 +280,84 @@ inline int parts_for(const Shape &sh, int dtype) {
 
 template <typename T>
 void launch_fwd(const void *x, const void *res, const float *gamma, const float *beta, const float *rmean, const float *rvar,
-                float eps, const Shape &sh, int relu, void *y, hipStream_t s) {
+                float eps, const Shape &sh, int relu, void *y, const int *rows_dev, hipStream_t s) {
   const dim3 grid(grid_for(sh, kMaxBlocks), col_tiles(sh));
-#define BFHIP_BN_EVAL_FWD(RES, RELU)                                                                                   \
-  hipLaunchKernelGGL((bn_eval_fwd_kernel<T, RES, RELU>), grid, dim3(kBlock), 0, s, (const T *)x, (const T *)res, gamma, \
-                     beta, rmean, rvar, eps, sh, (T *)y)
-  if (res) { if (relu) BFHIP_BN_EVAL_FWD(true, true); else BFHIP_BN_EVAL_FWD(true, false); }
-  else { if (relu) BFHIP_BN_EVAL_FWD(false, true); else BFHIP_BN_EVAL_FWD(false, false); }
+#define BFHIP_BN_EVAL_FWD(RES, RELU, ROWS)                                                                              \
+  hipLaunchKernelGGL((bn_eval_fwd_kernel<T, RES, RELU, ROWS>), grid, dim3(kBlock), 0, s, (const T *)x, (const T *)res, \
+                     gamma, beta, rmean, rvar, eps, sh, (T *)y, rows_dev)
+#define BFHIP_BN_EVAL_FWD_ACT(RES, ROWS)                                                      \
+  do {                                                                                        \
+    if (relu) BFHIP_BN_EVAL_FWD(RES, true, ROWS); else BFHIP_BN_EVAL_FWD(RES, false, ROWS);   \
+  } while (0)
+  if (rows_dev) { if (res) BFHIP_BN_EVAL_FWD_ACT(true, true); else BFHIP_BN_EVAL_FWD_ACT(false, true); }
+  else { if (res) BFHIP_BN_EVAL_FWD_ACT(true, false); else BFHIP_BN_EVAL_FWD_ACT(false, false); }
+#undef BFHIP_BN_EVAL_FWD_ACT
 #undef BFHIP_BN_EVAL_FWD
 }
 
 template <typename T>
 void launch_bwd(const void *dy, const void *y, const void *x, const float *gamma, const float *rmean, const float *rvar,
-                float eps, const Shape &sh, int relu, void *dx, void *dres, float *partial, int grid_x, hipStream_t s) {
+                float eps, const Shape &sh, int relu, void *dx, void *dres, float *partial, int grid_x, const int *rows_dev,
+                hipStream_t s) {
   const dim3 grid(grid_x, col_tiles(sh));
-#define BFHIP_BN_EVAL_BWD(RELU, AFF)                                                                                  \
-  hipLaunchKernelGGL((bn_eval_bwd_kernel<T, RELU, AFF>), grid, dim3(kBlock), 0, s, (const T *)dy, (const T *)y,        \
-                     (const T *)x, gamma, rmean, rvar, eps, sh, (T *)dx, (T *)dres, partial)
-  if (partial) { if (relu) BFHIP_BN_EVAL_BWD(true, true); else BFHIP_BN_EVAL_BWD(false, true); }
-  else { if (relu) BFHIP_BN_EVAL_BWD(true, false); else BFHIP_BN_EVAL_BWD(false, false); }
+#define BFHIP_BN_EVAL_BWD(RELU, AFF, ROWS)                                                                            \
+  hipLaunchKernelGGL((bn_eval_bwd_kernel<T, RELU, AFF, ROWS>), grid, dim3(kBlock), 0, s, (const T *)dy, (const T *)y,  \
+                     (const T *)x, gamma, rmean, rvar, eps, sh, (T *)dx, (T *)dres, partial, rows_dev)
+#define BFHIP_BN_EVAL_BWD_ACT(AFF, ROWS)                                                      \
+  do {                                                                                        \
+    if (relu) BFHIP_BN_EVAL_BWD(true, AFF, ROWS); else BFHIP_BN_EVAL_BWD(false, AFF, ROWS);   \
+  } while (0)
+  if (rows_dev) { if (partial) BFHIP_BN_EVAL_BWD_ACT(true, true); else BFHIP_BN_EVAL_BWD_ACT(false, true); }
+  else { if (partial) BFHIP_BN_EVAL_BWD_ACT(true, false); else BFHIP_BN_EVAL_BWD_ACT(false, false); }
+#undef BFHIP_BN_EVAL_BWD_ACT
 #undef BFHIP_BN_EVAL_BWD
+}
+
+// the two directions' host bodies; rows_dev = nullptr: every row is active
+int run_fwd(const char *what, const void *x, const void *residual, const float *gamma, const float *beta,
+            const float *running_mean, const float *running_var, long long M, int C, int dtype, float eps, int relu, void *y,
+            const int *rows_dev, hipStream_t stream) {
+  BFHIP_REQUIRE(shape_ok(M, C, dtype), "%s: unsupported M=%lld C=%d dtype=%d", what, M, C, dtype);
+  BFHIP_REQUIRE(x && y && gamma && beta && running_mean && running_var,
+                "%s: x, y, gamma, beta and the running statistics are required", what);
+  BFHIP_REQUIRE(aligned16(x) && aligned16(residual) && aligned16(y) && aligned16(gamma) && aligned16(beta) &&
+                    aligned16(running_mean) && aligned16(running_var),
+                "%s: tensors must be 16-byte aligned", what);
+  const Shape sh = make_shape(M, C, dtype);
+  if (dtype == 1)
+    launch_fwd<bf16_t>(x, residual, gamma, beta, running_mean, running_var, eps, sh, relu, y, rows_dev, stream);
+  else
+    launch_fwd<float>(x, residual, gamma, beta, running_mean, running_var, eps, sh, relu, y, rows_dev, stream);
+  return check_launch(what);
+}
+
+int run_bwd(const char *what, const void *dy, const void *y, const void *x, const float *gamma, const float *running_mean,
+            const float *running_var, long long M, int C, int dtype, float eps, int relu, void *dx, void *dres, float *partial,
+            float *dgb, const int *rows_dev, hipStream_t stream) {
+  BFHIP_REQUIRE(shape_ok(M, C, dtype), "%s: unsupported M=%lld C=%d dtype=%d", what, M, C, dtype);
+  BFHIP_REQUIRE(dy, "%s: dy is required", what);
+  BFHIP_REQUIRE(!relu || y, "%s: the ReLU mask needs y", what);
+  BFHIP_REQUIRE((x != nullptr) == (partial != nullptr) && (x != nullptr) == (dgb != nullptr),
+                "%s: x, partial and dgb are given together or not at all", what);
+  BFHIP_REQUIRE(dx || dres || partial, "%s: no output requested", what);
+  BFHIP_REQUIRE(!dx || (gamma && running_var), "%s: dx needs gamma and running_var", what);
+  BFHIP_REQUIRE(!partial || (running_mean && running_var), "%s: the parameter gradients need the running statistics", what);
+  BFHIP_REQUIRE(aligned16(dy) && aligned16(y) && aligned16(x) && aligned16(dx) && aligned16(dres) && aligned16(gamma) &&
+                    aligned16(running_mean) && aligned16(running_var) && aligned16(partial) && aligned16(dgb),
+                "%s: tensors must be 16-byte aligned", what);
+  const Shape sh = make_shape(M, C, dtype);
+  const int grid = partial ? parts_for(sh, dtype) : grid_for(sh, kMaxBlocks);
+  if (dtype == 1)
+    launch_bwd<bf16_t>(dy, relu ? y : nullptr, x, gamma, running_mean, running_var, eps, sh, relu, dx, dres, partial, grid,
+                       rows_dev, stream);
+  else
+    launch_bwd<float>(dy, relu ? y : nullptr, x, gamma, running_mean, running_var, eps, sh, relu, dx, dres, partial, grid,
+                      rows_dev, stream);
+  int rc = check_launch(what);
+  if (rc != BFHIP_OK || !partial) return rc;
+  hipLaunchKernelGGL(bn_eval_param_grad_kernel, dim3(ceil_div(2 * C, kWave)), dim3(kBlock), 0, stream, (const float *)partial,
+                     grid, 2 * C, dgb);
+  return check_launch("bn_eval_param_grad");
 }
 
 }  // namespace
@@ -292,45 +374,30 @@ BFHIP_EXPORT int bfhip_bn_eval_parts(long long M, int C, int dtype) {
 BFHIP_EXPORT int bfhip_bn_eval_fwd(const void *x, const void *residual, const float *gamma, const float *beta,
                                    const float *running_mean, const float *running_var, long long M, int C, int dtype, float eps,
                                    int relu, void *y, void *stream) {
-  BFHIP_REQUIRE(shape_ok(M, C, dtype), "bn_eval_fwd: unsupported M=%lld C=%d dtype=%d", M, C, dtype);
-  BFHIP_REQUIRE(x && y && gamma && beta && running_mean && running_var,
-                "bn_eval_fwd: x, y, gamma, beta and the running statistics are required");
-  BFHIP_REQUIRE(aligned16(x) && aligned16(residual) && aligned16(y) && aligned16(gamma) && aligned16(beta) &&
-                    aligned16(running_mean) && aligned16(running_var),
-                "bn_eval_fwd: tensors must be 16-byte aligned");
-  const Shape sh = make_shape(M, C, dtype);
-  if (dtype == 1)
-    launch_fwd<bf16_t>(x, residual, gamma, beta, running_mean, running_var, eps, sh, relu, y, (hipStream_t)stream);
-  else
-    launch_fwd<float>(x, residual, gamma, beta, running_mean, running_var, eps, sh, relu, y, (hipStream_t)stream);
-  return check_launch("bn_eval_fwd");
+  return run_fwd("bn_eval_fwd", x, residual, gamma, beta, running_mean, running_var, M, C, dtype, eps, relu, y, nullptr,
+                 (hipStream_t)stream);
 }
 
 BFHIP_EXPORT int bfhip_bn_eval_bwd(const void *dy, const void *y, const void *x, const float *gamma, const float *running_mean,
                                    const float *running_var, long long M, int C, int dtype, float eps, int relu, void *dx,
                                    void *dres, float *partial, float *dgb, void *stream) {
-  BFHIP_REQUIRE(shape_ok(M, C, dtype), "bn_eval_bwd: unsupported M=%lld C=%d dtype=%d", M, C, dtype);
-  BFHIP_REQUIRE(dy, "bn_eval_bwd: dy is required");
-  BFHIP_REQUIRE(!relu || y, "bn_eval_bwd: the ReLU mask needs y");
-  BFHIP_REQUIRE((x != nullptr) == (partial != nullptr) && (x != nullptr) == (dgb != nullptr),
-                "bn_eval_bwd: x, partial and dgb are given together or not at all");
-  BFHIP_REQUIRE(dx || dres || partial, "bn_eval_bwd: no output requested");
-  BFHIP_REQUIRE(!dx || (gamma && running_var), "bn_eval_bwd: dx needs gamma and running_var");
-  BFHIP_REQUIRE(!partial || (running_mean && running_var), "bn_eval_bwd: the parameter gradients need the running statistics");
-  BFHIP_REQUIRE(aligned16(dy) && aligned16(y) && aligned16(x) && aligned16(dx) && aligned16(dres) && aligned16(gamma) &&
-                    aligned16(running_mean) && aligned16(running_var) && aligned16(partial) && aligned16(dgb),
-                "bn_eval_bwd: tensors must be 16-byte aligned");
-  const Shape sh = make_shape(M, C, dtype);
-  const int grid = partial ? parts_for(sh, dtype) : grid_for(sh, kMaxBlocks);
-  if (dtype == 1)
-    launch_bwd<bf16_t>(dy, relu ? y : nullptr, x, gamma, running_mean, running_var, eps, sh, relu, dx, dres, partial, grid,
-                       (hipStream_t)stream);
-  else
-    launch_bwd<float>(dy, relu ? y : nullptr, x, gamma, running_mean, running_var, eps, sh, relu, dx, dres, partial, grid,
-                      (hipStream_t)stream);
-  int rc = check_launch("bn_eval_bwd");
-  if (rc != BFHIP_OK || !partial) return rc;
-  hipLaunchKernelGGL(bn_eval_param_grad_kernel, dim3(ceil_div(2 * C, kWave)), dim3(kBlock), 0, (hipStream_t)stream,
-                     (const float *)partial, grid, 2 * C, dgb);
-  return check_launch("bn_eval_param_grad");
+  return run_bwd("bn_eval_bwd", dy, y, x, gamma, running_mean, running_var, M, C, dtype, eps, relu, dx, dres, partial, dgb,
+                 nullptr, (hipStream_t)stream);
+}
+
+BFHIP_EXPORT int bfhip_bn_eval_rows_fwd(const void *x, const void *residual, const float *gamma, const float *beta,
+                                        const float *running_mean, const float *running_var, long long M, int C, int dtype,
+                                        float eps, int relu, void *y, const int *rows_dev, void *stream) {
+  BFHIP_REQUIRE(rows_dev, "bn_eval_rows_fwd: rows_dev is required");
+  return run_fwd("bn_eval_rows_fwd", x, residual, gamma, beta, running_mean, running_var, M, C, dtype, eps, relu, y, rows_dev,
+                 (hipStream_t)stream);
+}
+
+BFHIP_EXPORT int bfhip_bn_eval_rows_bwd(const void *dy, const void *y, const void *x, const float *gamma,
+                                        const float *running_mean, const float *running_var, long long M, int C, int dtype,
+                                        float eps, int relu, void *dx, void *dres, float *partial, float *dgb,
+                                        const int *rows_dev, void *stream) {
+  BFHIP_REQUIRE(rows_dev, "bn_eval_rows_bwd: rows_dev is required");
+  return run_bwd("bn_eval_rows_bwd", dy, y, x, gamma, running_mean, running_var, M, C, dtype, eps, relu, dx, dres, partial, dgb,
+                 rows_dev, (hipStream_t)stream);
 }

@@ -585,10 +585,78 @@ __global__ __launch_bounds__(64) void rnms_sweep_kernel(const unsigned long long
   if (lane == 0) *n_keep = kept < post_max ? kept : post_max;
 }
 
+// --------------------------------------------------------------------------------- packed predictions
+// The filter of TransFusionBBoxCoder.decode (BF/utils.py:100-124) as a stable compaction that leaves the counts on the device:
+// proposal p of sample b is kept iff its centre lies in [lo, hi] on all three axes and, with a threshold, score > thr (a NaN
+// fails every comparison).  One workgroup per sample walks the proposals in chunks of its size: wave ballot, the waves'
+// counts through LDS, slot = rows kept so far + kept lanes below.  Rows [count, P) are cleared (label -1).  No atomics.
+constexpr int kPackBlock = 256;
+__global__ __launch_bounds__(kPackBlock) void predict_compact_kernel(const float *__restrict__ boxes,
+                                                                     const float *__restrict__ scores,
+                                                                     const long long *__restrict__ labels, int P, int W,
+                                                                     float lx, float ly, float lz, float hx, float hy, float hz,
+                                                                     int use_thr, float thr, float *__restrict__ out_boxes,
+                                                                     float *__restrict__ out_scores, int *__restrict__ out_labels,
+                                                                     int *__restrict__ counts) {
+  constexpr int kWaves = kPackBlock / kWave;
+  __shared__ int wcnt[2][kWaves];  // by chunk parity: one barrier per chunk
+  const int b = blockIdx.x, t = threadIdx.x, lane = t & (kWave - 1), wv = t / kWave;
+  const size_t row0 = (size_t)b * P;
+  int base = 0;
+  for (int p0 = 0, it = 0; p0 < P; p0 += kPackBlock, it ^= 1) {
+    const int p = p0 + t;
+    bool keep = false;
+    float s = 0.f;
+    const float *src = boxes + (row0 + (p < P ? p : 0)) * W;
+    if (p < P) {
+      s = scores[row0 + p];
+      const float x = src[0], y = src[1], z = src[2];
+      keep = x >= lx && y >= ly && z >= lz && x <= hx && y <= hy && z <= hz && (!use_thr || s > thr);
+    }
+    const unsigned long long bal = __ballot(keep);
+    if (lane == 0) wcnt[it][wv] = __popcll(bal);
+    __syncthreads();
+    int before = 0, total = 0;
+#pragma unroll
+    for (int k = 0; k < kWaves; ++k) {
+      const int c = wcnt[it][k];
+      before += k < wv ? c : 0;
+      total += c;
+    }
+    if (keep) {  // slot <= p < P
+      const size_t slot = row0 + base + before + __popcll(bal & ((1ull << lane) - 1ull));
+      for (int j = 0; j < W; ++j) out_boxes[slot * W + j] = src[j];
+      out_scores[slot] = s;
+      out_labels[slot] = (int)labels[row0 + p];
+    }
+    base += total;
+  }
+  for (int p = base + t; p < P; p += kPackBlock) {
+    for (int j = 0; j < W; ++j) out_boxes[(row0 + p) * W + j] = 0.f;
+    out_scores[row0 + p] = 0.f;
+    out_labels[row0 + p] = -1;
+  }
+  if (t == 0) counts[b] = base;
+}
+
 }  // namespace
 }  // namespace bfhip
 
 using namespace bfhip;
+
+BFHIP_EXPORT int bfhip_predict_compact(const float *boxes, const float *scores, const long long *labels, int B, int P, int W,
+                                       const float *range_host, int use_threshold, float threshold, float *out_boxes,
+                                       float *out_scores, int32_t *out_labels, int32_t *counts, void *stream) {
+  BFHIP_REQUIRE(boxes && scores && labels && range_host && out_boxes && out_scores && out_labels && counts,
+                "predict_compact: null pointer");
+  BFHIP_REQUIRE(B > 0 && P > 0 && P <= 4096 && (W == 7 || W == 9), "predict_compact: bad sizes B=%d P=%d (<= 4096) W=%d (7 | 9)",
+                B, P, W);
+  BFHIP_REQUIRE(out_boxes != boxes && out_scores != scores, "predict_compact: the outputs must not alias the inputs");
+  hipLaunchKernelGGL(predict_compact_kernel, dim3(B), dim3(kPackBlock), 0, (hipStream_t)stream, boxes, scores, labels, P, W,
+                     range_host[0], range_host[1], range_host[2], range_host[3], range_host[4], range_host[5],
+                     use_threshold ? 1 : 0, threshold, out_boxes, out_scores, out_labels, counts);
+  return check_launch("predict_compact");
+}
 
 BFHIP_EXPORT int bfhip_circle_nms(const float *dets, int n, float thresh, int post_max_size, int32_t *keep,
                                   int32_t *n_keep, void *stream) {

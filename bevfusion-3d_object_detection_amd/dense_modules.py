@@ -745,9 +745,10 @@ class BEVFusionHead(nn.Module):
         metas = [getattr(d, "metainfo", None) for d in batch_data_samples]
         return self.loss_by_feat(self(batch_feats, metas), gts)
 
-    def predict_by_feat(self, preds_dicts, metas=None, img=None, rescale=False, for_roi=False):
+    def predict_by_feat(self, preds_dicts, metas=None, img=None, rescale=False, for_roi=False, packed=False):
         """BF/bevfusion_head.py:322-448 with nms_type None (the nuScenes configs): score = sigmoid(cls) * heat-map score
-        of the query's own class, decode with the score / centre-range filter.  One dict per sample."""
+        of the query's own class, decode with the score / centre-range filter.  One dict per sample; packed=True: the same
+        rows as a head_targets.PackedPredictions, compacted on the device without a host read (no NMS on that path)."""
         preds = preds_dicts[0][0]
         P = self.num_proposals
         score = preds["heatmap"][..., -P:].sigmoid()
@@ -755,6 +756,12 @@ class BEVFusionHead(nn.Module):
         score = score * preds["query_heatmap_score"] * one_hot
         vel = preds["vel"][..., -P:] if "vel" in preds else None
         nms_type = (self.test_cfg or {}).get("nms_type", None)
+        if packed:
+            if nms_type is not None:
+                raise ValueError("packed=True has no NMS: test_cfg['nms_type'] = %r stays on the list path (packed=False)"
+                                 % (nms_type,))
+            return self.bbox_coder.decode_packed(score, preds["rot"][..., -P:], preds["dim"][..., -P:],
+                                                 preds["center"][..., -P:], preds["height"][..., -P:], vel)
         rets = self.bbox_coder.decode(score, preds["rot"][..., -P:], preds["dim"][..., -P:], preds["center"][..., -P:],
                                       preds["height"][..., -P:], vel, filter=True)
         if nms_type is not None:
@@ -785,5 +792,5 @@ class BEVFusionHead(nn.Module):
             rets = out
         return [dict(bboxes_3d=r["bboxes"], scores_3d=r["scores"], labels_3d=r["labels"].int()) for r in rets]
 
-    def predict(self, batch_feats, batch_input_metas=None):
-        return self.predict_by_feat(self(batch_feats, batch_input_metas), batch_input_metas)
+    def predict(self, batch_feats, batch_input_metas=None, packed=False):
+        return self.predict_by_feat(self(batch_feats, batch_input_metas), batch_input_metas, packed=packed)

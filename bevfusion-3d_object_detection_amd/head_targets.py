@@ -136,6 +136,84 @@ class TransFusionBBoxCoder:
             out.append(dict(bboxes=boxes[i, cmask], scores=scores[i, cmask], labels=labels[i, cmask]))
         return out
 
+    def decode_packed(self, heatmap, rot, dim, center, height, vel):
+        """decode(filter=True) without its host reads: the same rows, compacted per sample on the device
+        (bfhip_predict_compact) into a PackedPredictions.  Scores and labels come from the same `max(1)`."""
+        if self.post_center_range is None:
+            raise NotImplementedError("Need to reorganize output as a batch, only support post_center_range is not None for now!")
+        scores, labels = heatmap.max(1)
+        boxes = self.decode_boxes(rot, dim, center, height, vel)
+        return PackedPredictions(*predict_compact(boxes, scores, labels, self.post_center_range, self.score_threshold))
+
+
+# ----------------------------------------------------------------------------------------------- packed predictions
+def torch_predict_compact(boxes, scores, labels, post_center_range, score_threshold=None):
+    """The definition of bfhip_predict_compact in torch ops (and the CPU path).  boxes f32[B,P,W], scores f32[B,P], labels [B,P].
+    A row is kept iff its centre is inside post_center_range (bounds included) on all three axes and, when score_threshold is
+    truthy (None and 0.0 are not: TransFusionBBoxCoder.decode's `if self.score_threshold:`), score > score_threshold; NaN fails
+    every comparison.  Kept rows keep their order.  -> out_boxes f32[B,P,W], out_scores f32[B,P], out_labels i32[B,P] (rows >=
+    count: zeros, label -1), counts i32[B].  No host read."""
+    B, P, _ = boxes.shape
+    rng = torch.as_tensor(post_center_range, device=boxes.device, dtype=boxes.dtype)
+    keep = (boxes[..., :3] >= rng[:3]).all(2) & (boxes[..., :3] <= rng[3:]).all(2)
+    if score_threshold:
+        keep = keep & (scores > score_threshold)
+    counts = keep.sum(1)
+    order = torch.sort((~keep).to(torch.uint8), dim=1, stable=True).indices  # kept rows first, each group in proposal order
+    live = torch.arange(P, device=boxes.device)[None, :] < counts[:, None]
+    out_boxes = torch.where(live[..., None], torch.gather(boxes, 1, order[..., None].expand_as(boxes)), 0.0)
+    out_scores = torch.where(live, torch.gather(scores, 1, order), 0.0)
+    out_labels = torch.where(live, torch.gather(labels, 1, order).to(torch.int32), -1)
+    return out_boxes, out_scores, out_labels, counts.to(torch.int32)
+
+
+def predict_compact(boxes, scores, labels, post_center_range, score_threshold=None):
+    """torch_predict_compact on the device in one launch (csrc/head.hip: wave ballots + a workgroup prefix scan, P <= 4096);
+    host tensors take the torch definition."""
+    if not boxes.is_cuda:
+        return torch_predict_compact(boxes, scores, labels, post_center_range, score_threshold)
+    B, P, W = boxes.shape
+    boxes, scores, labels = _f32c(boxes), _f32c(scores), labels.detach().long().contiguous()
+    out_boxes, out_scores = torch.empty_like(boxes), torch.empty_like(scores)
+    out_labels = torch.empty(B, P, dtype=torch.int32, device=boxes.device)
+    counts = torch.empty(B, dtype=torch.int32, device=boxes.device)
+    with torch.cuda.device(boxes.device):
+        _lib.call("bfhip_predict_compact", _lib.ptr(boxes), _lib.ptr(scores), _lib.ptr(labels), B, P, W,
+                  _lib.host_f32(post_center_range[:6]), 1 if score_threshold else 0, float(score_threshold or 0.0),
+                  _lib.ptr(out_boxes), _lib.ptr(out_scores), _lib.ptr(out_labels), _lib.ptr(counts), _lib.stream_of(boxes))
+    return out_boxes, out_scores, out_labels, counts
+
+
+class PackedPredictions:
+    """The predictions of a batch without a host read: boxes f32[B,P,W], scores f32[B,P], labels i32[B,P] hold each sample's
+    kept rows as a prefix (the rest: zeros, label -1), counts i32[B] their numbers; overflow is the static capacity mode's
+    device flag of the forward that produced them (0-dim bool; None outside that mode)."""
+
+    def __init__(self, boxes, scores, labels, counts, overflow=None):
+        self.boxes, self.scores, self.labels, self.counts, self.overflow = boxes, scores, labels, counts, overflow
+
+    def __len__(self):
+        return int(self.boxes.shape[0])
+
+    def to_list(self, on_overflow="warn"):
+        """The list `predict` returns (one dict of bboxes_3d / scores_3d / labels_3d per sample) after ONE device -> host copy:
+        the counts and the overflow flag together.  An overflowed forward dropped LiDAR rows beyond a capacity, so its
+        predictions are the truncated frame's: on_overflow = "warn" | "raise" | "ignore"."""
+        if on_overflow not in ("warn", "raise", "ignore"):
+            raise ValueError("on_overflow must be 'warn', 'raise' or 'ignore', not %r" % (on_overflow,))
+        head = self.counts
+        if self.overflow is not None:
+            head = torch.cat([head, self.overflow.reshape(1).to(head.dtype)])
+        head = head.tolist()
+        if self.overflow is not None and head[-1] and on_overflow != "ignore":
+            msg = "predictions of a frame that exceeded a LiDAR row capacity (rows beyond it were dropped)"
+            if on_overflow == "raise":
+                raise RuntimeError(msg)
+            import warnings
+            warnings.warn(msg)
+        return [dict(bboxes_3d=self.boxes[i, :n], scores_3d=self.scores[i, :n], labels_3d=self.labels[i, :n])
+                for i, n in zip(range(len(self)), head)]
+
 
 # ----------------------------------------------------------------------------------------------- assignment
 def _assigner_weights(assigner_cfg):

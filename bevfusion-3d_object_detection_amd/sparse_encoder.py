@@ -112,6 +112,7 @@ class BEVFusionSparseEncoder(nn.Module):
         # problem's: BEVFusion.loss poisons the step's losses with it instead of training on that map)
         self.capacity_status = None
         self._caps_dev = (None, None)
+        self._static_eval = False  # the BatchNorms have been told to accept capacity-sized matrices in eval mode
         first_order = ("conv",) if order[0] != "conv" else order  # pre-activation variant keeps a bare first conv
         self.conv_input = make_sparse_convmodule(in_channels, base_channels, 3, norm_cfg=norm_cfg, padding=1,
                                                  indice_key="subm1", conv_type="SubMConv3d", order=first_order)
@@ -164,6 +165,12 @@ class BEVFusionSparseEncoder(nn.Module):
         x = SparseConvTensor(voxel_features, coors, self.sparse_shape, batch_size)
         if n_valid is not None:
             assert self.static_caps is not None, "static capacity mode needs capacities (run one exact forward first)"
+            if not self.training and not self._static_eval:
+                # eval: the BatchNorms mask the rows beyond the count themselves (running statistics, csrc/bn_eval.hip)
+                for m in self.modules():
+                    if isinstance(m, BatchNorm1dAct):
+                        m.static_eval = True
+                self._static_eval = True
             seen = self._monitor.poll()  # true counts of an EARLIER forward, if they have arrived: no stall
             if seen is not None:
                 if any(n > c for n, c in zip(seen, self.static_caps)):

@@ -582,6 +582,9 @@ class BatchNorm1dAct(nn.BatchNorm1d):
     is advanced lazily like bn2d._LazyBatchCounter's (a host counter flushed into the buffer when the state dict is read)."""
 
     _pending_batches = 0
+    # eval mode on capacity-sized matrices (forward(..., rows_dev=) with the module in eval): opt-in per module, switched on by
+    # the sparse encoder when it runs its static capacity path in eval.  Off, such a call raises as it always has.
+    static_eval = False
 
     def _flush_batches(self):
         if self._pending_batches and self.num_batches_tracked is not None:
@@ -593,7 +596,8 @@ class BatchNorm1dAct(nn.BatchNorm1d):
         super()._save_to_state_dict(destination, prefix, keep_vars)
 
     def forward(self, x, residual=None, relu=False, rows_dev=None):
-        """rows_dev (static capacity mode): device i32[1] count of ACTIVE rows; the rows beyond it are zeros on entry."""
+        """rows_dev (static capacity mode): device i32[1] count of ACTIVE rows; the rows beyond it are zeros on entry.  In eval
+        mode (static_eval) they may hold anything and come out as zeros."""
         C = x.shape[1] if x.dim() == 2 else 0
         if (FUSED_BN1D and self.training and x.is_cuda and x.dim() == 2 and x.dtype == torch.bfloat16 and x.shape[0] > 1
                 and self.affine and self.track_running_stats and self.momentum is not None and C % 8 == 0):
@@ -616,17 +620,27 @@ class BatchNorm1dAct(nn.BatchNorm1d):
                                 self.momentum, relu)
             return _BN1dFunction.apply(x, residual, self.weight, self.bias, self.running_mean, self.running_var, self.eps,
                                        self.momentum, relu, rows_dev)
-        if rows_dev is not None:
+        if rows_dev is not None and not (self.static_eval and not self.training and x.dim() == 2 and self.track_running_stats):
+            # batch statistics over a capacity-sized matrix need the fused kernels' row count; eval mode masks the rows itself
+            # once the owner of the module has opted in (static_eval)
             raise RuntimeError("capacity-sized feature matrices need the fused BatchNorm kernels (training mode, supported width)")
         self._flush_batches()
         if not self.training and x.dim() == 2:
             from . import bn2d
             if bn2d._eval_fusable(self, x) and bn2d._eval_residual_ok(x, residual):
-                return bn2d.eval_apply(self, x, residual, relu)  # running statistics: csrc/bn_eval.hip (BFHIP_BN_EVAL)
+                # running statistics: csrc/bn_eval.hip (BFHIP_BN_EVAL); with rows_dev the rows beyond the count come out zero
+                return bn2d.eval_apply(self, x, residual, relu, rows_dev)
+        live = None
+        if rows_dev is not None:
+            # a*x + b would turn the padding rows into b: select zeros there, on the way out and (so that no NaN of a padding row
+            # reaches the parameter gradients) on the way in.  No host read
+            live = (torch.arange(x.shape[0], device=x.device) < rows_dev)[:, None]
+            x = torch.where(live, x, 0.0)
         out = super().forward(x)
         if residual is not None:
             out = out + residual
-        return torch.relu(out) if relu else out
+        out = torch.relu(out) if relu else out
+        return out if live is None else torch.where(live, out, 0.0)
 
 
 class SparseModule(nn.Module):

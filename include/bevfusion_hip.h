@@ -445,10 +445,20 @@ int bfhip_maxpool3x3s2_bwd(const void *dy, const unsigned char *tap, int N, int 
  *                  grad f32[n] <- d element loss / d logit (unscaled)
  *   query_losses   loss_sums f32[2] <- (weighted focal sum over [B,P,C], weighted L1 sum over [B,P,K]); grad_cls /
  *                  grad_box in the layout of the inputs (entries outside [p_off, p_off+P) untouched)
+ *   predict_compact  the filter of TransFusionBBoxCoder.decode (BF/utils.py:100-124) with the counts left on the device:
+ *                  boxes f32[B,P,W] (W = 7 | 9, decoded), scores f32[B,P], labels i64[B,P] (what max(1) returns), P <= 4096;
+ *                  range_host = post_center_range {x0, y0, z0, x1, y1, z1}.  A row is kept iff lo <= centre <= hi on all three
+ *                  axes and, when use_threshold != 0, score > threshold; NaN fails every comparison.  Kept rows go, in
+ *                  ascending proposal order, to out_boxes f32[B,P,W], out_scores f32[B,P], out_labels i32[B,P]; rows >=
+ *                  counts[b] are zeros with label -1; counts i32[B].  One launch, one workgroup per sample, no atomics, no
+ *                  host read.  The outputs must not alias the inputs.
  * --------------------------------------------------------------------------------------- */
 int bfhip_decode_boxes(const float *center, const float *height, const float *dim, const float *rot,
                        const float *vel, int B, int P, int ld, int p_off, const float *cfg_host, float *boxes,
                        void *stream);
+int bfhip_predict_compact(const float *boxes, const float *scores, const long long *labels, int B, int P, int W,
+                          const float *range_host, int use_threshold, float threshold, float *out_boxes, float *out_scores,
+                          int32_t *out_labels, int32_t *counts, void *stream);
 int bfhip_assign_cost(const float *boxes, int W, const float *cls_logits, int C, int ld, int p_off,
                       const float *gt_boxes, int Wg, const int32_t *gt_labels, const int32_t *n_gt, int B, int P,
                       int G, const float *cfg_host, float *cost, float *iou, void *stream);
@@ -694,6 +704,25 @@ int bfhip_bn_eval_fwd(const void *x, const void *residual, const float *gamma, c
 int bfhip_bn_eval_bwd(const void *dy, const void *y, const void *x, const float *gamma, const float *running_mean,
                       const float *running_var, long long M, int C, int dtype, float eps, int relu, void *dx, void *dres,
                       float *partial, float *dgb, void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Eval-mode BatchNorm over a CAPACITY-sized [M, C] matrix whose active rows are a prefix counted on the device
+ *   (csrc/bn_eval.hip; the static capacity mode of the sparse encoder in eval).  Same arguments and shapes as
+ *   bfhip_bn_eval_fwd / _bwd plus rows_dev, a device i32[1]; with n = min(max(*rows_dev, 0), M):
+ *   fwd   rows < n get what bfhip_bn_eval_fwd computes, bit for bit; rows [n, M) are WRITTEN AS ZEROS whatever x and residual
+ *         hold there (NaN included).
+ *   bwd   rows < n as bfhip_bn_eval_bwd; rows >= n get dx = dres = 0 and add nothing to dgamma / dbeta.  partial has
+ *         bfhip_bn_eval_parts(M, C, dtype) rows (the partition of the capacity), so dgb equals, bit for bit, what
+ *         bfhip_bn_eval_bwd gives on the same matrix with dy zeroed beyond n.  No atomics: run-to-run reproducible.
+ *   The kernels read the count themselves (one uniform load per workgroup): no extra launch, workspace, allocation or
+ *   synchronisation; everything runs on `stream`.  bfhip_bn_eval_supported(M, C, dtype) decides the shapes.
+ * --------------------------------------------------------------------------------------- */
+int bfhip_bn_eval_rows_fwd(const void *x, const void *residual, const float *gamma, const float *beta,
+                           const float *running_mean, const float *running_var, long long M, int C, int dtype, float eps,
+                           int relu, void *y, const int32_t *rows_dev, void *stream);
+int bfhip_bn_eval_rows_bwd(const void *dy, const void *y, const void *x, const float *gamma, const float *running_mean,
+                           const float *running_var, long long M, int C, int dtype, float eps, int relu, void *dx, void *dres,
+                           float *partial, float *dgb, const int32_t *rows_dev, void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * Camera-image preprocessing (csrc/preprocess.hip): the image path of the reference's Det3DDataPreprocessor
