@@ -181,6 +181,16 @@ SIGNATURES = {
     "bfhip_jpeg_forward": (_c_int, [_c_vp, _c_vp, _c_int, _c_vp, _c_sz, _c_vp, _c_sz, _c_vp]),
     "bfhip_jpeg_entropy_encode_device": (_c_int, [_c_vp, _c_vp, _c_int, _c_vp, _c_sz, _c_vp, _c_sz, _c_vp, _c_sz, _c_vp, _c_vp]),
     "bfhip_jpeg_encode": (_c_int, [_c_vp, _c_vp, _c_int, _c_vp, _c_sz, _c_vp, _c_sz, _c_vp, _c_sz, _c_vp, _c_sz, _c_vp, _c_vp]),
+    "bfhip_png_encode_supported": (_c_int, [_c_int] * 3),
+    "bfhip_png_encode_max_frames": (_c_int, []),
+    "bfhip_png_workspace_bytes": (_c_sz, [ctypes.c_int64, ctypes.c_int64, _c_int]),
+    "bfhip_png_capacity": (_c_sz, [ctypes.c_int64, ctypes.c_int64]),
+    "bfhip_png_result_words": (_c_sz, [ctypes.c_int64, ctypes.c_int64]),
+    "bfhip_png_encode": (_c_int, [_c_vp, _c_vp, _c_int, _c_vp, _c_sz, _c_vp, _c_sz, _c_vp, _c_sz, _c_vp, _c_sz, _c_vp]),
+    "bfhip_png_deflate": (_c_int, [_c_vp, _c_vp, _c_int, _c_vp, _c_sz, _c_vp, _c_sz, _c_vp, _c_sz, _c_vp, _c_sz, _c_vp]),
+    "bfhip_png_filter_host": (_c_int, [_c_vp, _c_int, _c_int, _c_vp, _c_sz]),
+    "bfhip_png_huffman_lengths": (_c_int, [_c_vp, _c_int, _c_int, _c_vp]),
+    "bfhip_png_deflate_host": (_c_int, [_c_vp, _c_sz, _c_sz, _c_vp, _c_sz, _c_vp, _c_sz, _c_vp]),
     "bfhip_points_in_boxes_block": (_c_int, []),
     "bfhip_points_in_boxes_max_boxes": (_c_int, []),
     "bfhip_points_in_boxes_workspace_bytes": (_c_sz, [ctypes.c_longlong, _c_int]),

@@ -1079,6 +1079,67 @@ int bfhip_jpeg_encode(const bfhip_jpeg_enc_frame *frames_host, const bfhip_jpeg_
                       size_t workspace_bytes, uint8_t *out_dev, size_t out_bytes, int64_t *result_dev, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Lossless PNG encode (csrc/png_encode_host.h, csrc/png_encode.hip): 8-bit RGB frames -> the zlib stream of a PNG file's IDAT
+ *   chunk, in a restricted DEFLATE that runs in parallel.  bevfusion_amd/png_encode.py defines the format byte for byte.
+ *   Filter: per row the type (None, Sub, Up, Average, Paeth over the RAW row above) with the least sum of v < 128 ? v : 256 - v
+ *     over its filtered bytes, the lowest type on a tie; the row above the first and the bytes left of the first pixel are
+ *     zero.  Filtered data: [height, 1 + 3 width], the type in front of each row.
+ *   Stream: 78 01, then one DEFLATE block per band of band_bytes filtered bytes, each band on a byte boundary.  Tokens: a
+ *     maximal stretch of equal bytes inside a band is a literal, matches of distance 1 and length min(r, 258) while r >= 3
+ *     bytes remain, then 0-2 literals.  A band is a dynamic block (HLIT 29, HDIST 0, HCLEN 15; code-length symbols 0-15 on four
+ *     bits; a 15-bit length-limited code from package-merge over the band's 286-symbol histogram, ties by symbol index; one
+ *     distance code of one bit when the band has a match) followed, unless it is the last, by an empty stored block (00 00 FF
+ *     FF); or, when that is not smaller than n + 5 ceil(n / 65535) bytes, stored blocks.  A stream therefore never exceeds
+ *     bfhip_png_capacity(n_bytes, band_bytes) = 2 + the sum of that bound over its bands.  The Adler-32 trailer is NOT written:
+ *     the caller combines it from the per-band (A, B, n) triples and appends it, as it writes the PNG chunks and their CRCs.
+ *   bfhip_png_frame: src_off: bytes from rgb_dev of the uint8 [height, width, 3] pixels (encode) or from data_dev of the bytes
+ *     (deflate: width and height are not read).  out_off / capacity: bytes from out_dev of the stream and how many it may take.
+ *     ws_off: bytes from the workspace, a multiple of 256, of bfhip_png_workspace_bytes(n_bytes, band_bytes, with_filter) bytes.
+ *     res_off: uint32 words from result_dev of the job's bfhip_png_result_words(n_bytes, band_bytes) words: stream length (low,
+ *     high word; the NEEDED length on overflow), flags (BFHIP_PNG_OVERFLOW: nothing was written at or past out_off + capacity),
+ *     stored bands, dynamic bands, longest code, bands, 0; then per band Adler A, B of the band alone, its length, its bytes in
+ *     the stream | stored << 31.  n_bytes: 1 .. 2^31 - 1, for encode height (1 + 3 width).  band_bytes: 1 .. 2^26, for encode
+ *     a whole number of rows.  Jobs in ascending order of out_off, ws_off and res_off without overlap; at most
+ *     bfhip_png_encode_max_frames() = 65535 of them; the host copy of the table is validated before anything is launched.
+ *   bfhip_png_encode: four launches whatever the batch (filter; per band histogram, Adler sums, code construction, decision and
+ *     emission into the band's slab, which the kernel zeroes itself; band offsets and results; compaction).  bfhip_png_deflate:
+ *     the last three over bytes already on the device.  Integer arithmetic only (integer atomic OR and LDS adds, which
+ *     commute): the same bytes on every run.  No allocation, no synchronisation; everything runs on `stream`.
+ *   HOST ONLY, no HIP call: bfhip_png_filter_host, bfhip_png_huffman_lengths (lens[n_symbols], n_symbols <= 286, max_len <= 15)
+ *     and bfhip_png_deflate_host (bands: 4 words per band as above, may be NULL; BFHIP_E_INVALID with nothing written at or past
+ *     `capacity` when the stream is longer, stats->bytes then holds the needed length).
+ * --------------------------------------------------------------------------------------- */
+#define BFHIP_PNG_OVERFLOW 1
+typedef struct bfhip_png_stats {
+  int64_t bytes;
+  int64_t bands, stored_bands, dynamic_bands;
+  int64_t tokens;
+  int32_t max_code_length, overflow;
+} bfhip_png_stats;
+typedef struct bfhip_png_frame {
+  int64_t src_off;
+  int64_t out_off, capacity;
+  int64_t ws_off, res_off;
+  int64_t n_bytes, band_bytes;
+  int32_t width, height;
+} bfhip_png_frame;
+int bfhip_png_encode_supported(int width, int height, int band_rows);
+int bfhip_png_encode_max_frames(void);
+size_t bfhip_png_workspace_bytes(int64_t n_bytes, int64_t band_bytes, int with_filter);
+size_t bfhip_png_capacity(int64_t n_bytes, int64_t band_bytes);
+size_t bfhip_png_result_words(int64_t n_bytes, int64_t band_bytes);
+int bfhip_png_encode(const bfhip_png_frame *frames_host, const bfhip_png_frame *frames_dev, int n_frames, const uint8_t *rgb_dev,
+                     size_t rgb_bytes, void *workspace, size_t workspace_bytes, uint8_t *out_dev, size_t out_bytes,
+                     uint32_t *result_dev, size_t result_words, void *stream);
+int bfhip_png_deflate(const bfhip_png_frame *jobs_host, const bfhip_png_frame *jobs_dev, int n_jobs, const uint8_t *data_dev,
+                      size_t data_bytes, void *workspace, size_t workspace_bytes, uint8_t *out_dev, size_t out_bytes,
+                      uint32_t *result_dev, size_t result_words, void *stream);
+int bfhip_png_filter_host(const uint8_t *rgb, int width, int height, uint8_t *out, size_t out_bytes);
+int bfhip_png_huffman_lengths(const uint32_t *hist, int n_symbols, int max_len, uint8_t *lens);
+int bfhip_png_deflate_host(const uint8_t *data, size_t n, size_t band_bytes, uint8_t *out, size_t capacity, uint32_t *bands,
+                           size_t band_slots, bfhip_png_stats *stats);
+
+/* ---------------------------------------------------------------------------------------
  * Points in rotated boxes, per box (csrc/points_in_boxes.hip): box_np_ops.points_in_rbbox (M3D/structures/ops/box_np_ops.py
  *   :354-377, 643-677) and the per-box gathers of the ground-truth database builder (tools/dataset_converters/
  *   create_gt_database.py:257, 296-297), as bevfusion_amd/box_ops.py: torch_points_in_boxes defines them.

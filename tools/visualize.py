@@ -3,7 +3,7 @@
 
     visualize.py RESULTS.pkl ANN_FILE --out DIR [--data-root ROOT] [--classes car,truck,...] [--threshold 0.01] [--gt]
                  [--only-classes car truck] [--cam-order 0 1 2] [--scale 3] [--max-vis 10] [--no-track] [--device cuda:0|cpu]
-                 [--video OUT.avi] [--fps 2] [--quality 90] [--video-stream cameras|bev] [--no-png]
+                 [--video OUT.avi] [--fps 2] [--quality 90] [--video-stream cameras|bev] [--no-png] [--png-encoder pillow|device]
     visualize.py --synthetic --out DIR [--frames 3] [--scale 3] [--small]
 
 RESULTS.pkl: the list tools/evaluate.py takes, one entry per sample with 'sample_idx' and 'pred_instances_3d' {'bboxes_3d',
@@ -12,7 +12,9 @@ RESULTS.pkl: the list tools/evaluate.py takes, one entry per sample with 'sample
 num_pts_feats), relative to --data-root.  --gt draws the infos' `instances` instead of the predictions (no tracking), as the
 reference tool does without --show-pred.  Predictions pass a score threshold, the class filter and the light tracker
 (bevfusion_amd.visualize.Tracker3D).  Out: DIR/cameras/000000.png ... and DIR/bev/000000.png ..., written with Pillow
-(--no-png: not written).  --video OUT.avi also writes the camera mosaics (--video-stream bev: the BEV plots) as a video, as the
+(--no-png: not written); --png-encoder device writes them with bevfusion_amd.png_encode instead: lossless too, the same pixels in a
+file of its own making, encoded on the device from the tensor the renderer left there, without copying the pixels to the host
+(on a machine without a GPU its host path writes the same bytes).  --video OUT.avi also writes the camera mosaics (--video-stream bev: the BEV plots) as a video, as the
 reference tools do -- they encode mp4v into an mp4 with OpenCV; here every frame is a baseline JPEG, encoded on the device from
 the tensor the renderer left there (bevfusion_amd.jpeg_encode.encode_frames), in an AVI file (MjpegAviWriter).
 --synthetic draws seeded frames, sweeps and boxes of the nominal six-camera rig instead (--small: 90 x 160 frames)."""
@@ -29,6 +31,7 @@ import torch
 
 import bevfusion_amd  # noqa: F401
 from bevfusion_amd import jpeg_encode
+from bevfusion_amd import png_encode
 from bevfusion_amd import synthetic
 from bevfusion_amd import visualize as vz
 
@@ -97,6 +100,8 @@ def main(argv=None):
     ap.add_argument("--quality", type=int, default=90, help="JPEG quality of the video's frames")
     ap.add_argument("--video-stream", choices=("cameras", "bev"), default="cameras")
     ap.add_argument("--no-png", action="store_true", help="with --video: write no PNG frames")
+    ap.add_argument("--png-encoder", choices=("pillow", "device"), default="pillow",
+                    help="who writes the PNG frames: Pillow from a host copy, or bevfusion_amd.png_encode from the device tensor")
     ap.add_argument("--synthetic", action="store_true")
     ap.add_argument("--small", action="store_true")
     ap.add_argument("--frames", type=int, default=3)
@@ -115,7 +120,7 @@ def main(argv=None):
         ap.error("RESULTS.pkl and ANN_FILE, or --synthetic")
     if args.no_png and not args.video:
         ap.error("--no-png needs --video")
-    if not args.no_png:
+    if not args.no_png and args.png_encoder == "pillow":
         from PIL import Image
     classes = args.classes.split(",") if args.classes else NUSC_CLASSES
     dev = torch.device(args.device)
@@ -135,14 +140,19 @@ def main(argv=None):
             if writer is None:
                 writer = jpeg_encode.MjpegAviWriter(args.video, args.fps, shown.shape[1], shown.shape[0])
             writer.write(data)
-        for sub, img in (("cameras", mosaic), ("bev", bev)):
-            if img is not None and not args.no_png:
-                os.makedirs(os.path.join(args.out, sub), exist_ok=True)
+        todo = [(sub, img) for sub, img in (("cameras", mosaic), ("bev", bev)) if img is not None and not args.no_png]
+        for sub, img in todo:
+            os.makedirs(os.path.join(args.out, sub), exist_ok=True)
+            if args.png_encoder == "pillow":
                 Image.fromarray(img.cpu().numpy()).save(os.path.join(args.out, sub, "%06d.png" % i))
+        if todo and args.png_encoder == "device":  # both images in one batch
+            png_encode.write_frames([os.path.join(args.out, sub, "%06d.png" % i) for sub, _ in todo], [img for _, img in todo])
         written += 1
     if writer is not None:
         writer.close()
         print("%d frames in %s (%s path)" % (len(writer.index), args.video, "kernel" if jpeg_encode.PATHS["kernel"] else "host"))
+    if args.png_encoder == "device" and not args.no_png:
+        print("png: %s path" % ("kernel" if png_encode.PATHS["kernel"] else "host"))
     print("%d samples written under %s (%s path)" % (written, args.out, "kernel" if vz.PATHS["kernel"] else "host"))
     return 0
 
