@@ -64,6 +64,12 @@ __device__ __forceinline__ void box_corners(float xc, float yc, float w, float h
   c[3] = {xc - ux + vx, yc - uy + vy};
 }
 
+// p within `tol` of the rectangle with centre (xc, yc), unit axes u, v and sides w, h
+__device__ __forceinline__ bool in_box(P2 p, float xc, float yc, P2 u, P2 v, float w, float h, float tol) {
+  P2 d = {p.x - xc, p.y - yc};
+  return fabsf(dot2(d, u)) <= w * 0.5f + tol && fabsf(dot2(d, v)) <= h * 0.5f + tol;
+}
+
 // area of the intersection of two rotated rectangles (x, y, w, h, angle)
 __device__ float rotated_intersection(float x1, float y1, float w1, float h1, float a1, float x2, float y2,
                                       float w2, float h2, float a2) {
@@ -72,8 +78,11 @@ __device__ float rotated_intersection(float x1, float y1, float w1, float h1, fl
   P2 c1[4], c2[4], u1, v1, u2, v2;
   box_corners(x1, y1, w1, h1, a1, c1, u1, v1);
   box_corners(x2, y2, w2, h2, a2, c2, u2, v2);
+  // Vertices of the intersection: edge x edge crossings and the corners of either box inside the other.  Each of the 16 edge
+  // pairs adds at most one point and each of the 8 corners at most one, whatever the tests below decide: n <= 24.
   P2 pts[24];
   int n = 0;
+  const float tol = 1e-5f;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     P2 A = c1[i], d1 = {c1[(i + 1) & 3].x - A.x, c1[(i + 1) & 3].y - A.y};
@@ -84,16 +93,21 @@ __device__ float rotated_intersection(float x1, float y1, float w1, float h1, fl
       if (fabsf(det) <= 1e-14f) continue;
       P2 ac = {C.x - A.x, C.y - A.y};
       float t1 = cross2(ac, d2) / det, t2 = cross2(ac, d1) / det;
-      if (t1 >= 0.f && t1 <= 1.f && t2 >= 0.f && t2 <= 1.f) pts[n++] = {A.x + t1 * d1.x, A.y + t1 * d1.y};
+      if (!(t1 >= 0.f && t1 <= 1.f && t2 >= 0.f && t2 <= 1.f)) continue;
+      // Edges that are parallel or collinear up to rounding (same yaw, yaw + pi/2, yaw + pi: lined-up or touching boxes)
+      // get here with det = rounding noise of size |d1| |d2| 1e-7, far above the absolute threshold, and t1, t2 = noise / noise:
+      // any value in [0, 1] used to become a vertex, up to IoU 0.8 for disjoint boxes.  Such a point lies on box 1's edge but
+      // anywhere along it; a vertex of the intersection lies in both boxes.  So a crossing counts only inside both, by the test
+      // and tolerance of the corners below.  Collinear overlaps are then described by the corners alone; a noise point that
+      // still passes lies on the boundary of the intersection and does not change its area.
+      P2 X = {A.x + t1 * d1.x, A.y + t1 * d1.y};
+      if (in_box(X, x1, y1, u1, v1, w1, h1, tol) && in_box(X, x2, y2, u2, v2, w2, h2, tol)) pts[n++] = X;
     }
   }
-  const float tol = 1e-5f;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    P2 d = {c1[i].x - x2, c1[i].y - y2};
-    if (fabsf(dot2(d, u2)) <= w2 * 0.5f + tol && fabsf(dot2(d, v2)) <= h2 * 0.5f + tol) pts[n++] = c1[i];
-    P2 e = {c2[i].x - x1, c2[i].y - y1};
-    if (fabsf(dot2(e, u1)) <= w1 * 0.5f + tol && fabsf(dot2(e, v1)) <= h1 * 0.5f + tol) pts[n++] = c2[i];
+    if (in_box(c1[i], x2, y2, u2, v2, w2, h2, tol)) pts[n++] = c1[i];
+    if (in_box(c2[i], x1, y1, u1, v1, w1, h1, tol)) pts[n++] = c2[i];
   }
   if (n < 3) return 0.f;
   float cx = 0.f, cy = 0.f;

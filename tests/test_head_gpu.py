@@ -1,7 +1,7 @@
 """GPU parity of csrc/head.hip (TransFusion head targets + losses) against oracle/head_oracle.py,
 scipy's linear_sum_assignment (the reference's own Hungarian step) and the reference outputs in tests/golden/head_ref.npz.
 Tolerances: assignment / labels / heat-map bit-exact; fp32 transcendental chains 1e-5; IoU 2e-4 abs (fp32 polygon
-clipping vs the fp64 oracle)."""
+clipping vs the fp64 oracle).  Structured geometry (identical, touching, collinear, nested boxes): tests/test_head_iou_gpu.py."""
 import os
 
 import numpy as np
